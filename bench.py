@@ -46,6 +46,10 @@ Prints ONE JSON line (rank 0) with
   `config.other_workloads`  BASELINE configs 3 and 4 and the reference's default BOTH_OBSERVATIONS mode (1-GPU run only);
   `cpu_baseline`  the CPU oracle (a port of the reference's algorithm) timed on this box's host cores on a bounded sample.
 
+The printed line leaves out the extra legs' own records (their figures are in `summary_at_the_end_of_the_line`) and the store probe's
+sweeps; `--details FILE` writes the full record.  `--dump-outputs DIR` writes what the headline's last timed step handed back (a fixed,
+seeded sample of the envs, float32 .npy files, at most 64 MB), so that two builds can be compared output for output.
+
 `--dry-run` is the launcher's self-test: same process / rendezvous / sharding / reduction code over gloo with a stub in
 place of the env, no GPU, no measurement (`value` is null) -- what tests/test_bench_launcher_cpu.py runs.
 """
@@ -314,10 +318,19 @@ def parse_args(argv=None):
     ap.add_argument('--no-trajectory-leg', action='store_true', help='skip config.trajectory (the rollout into a 64-slot trajectory buffer, sgx_step_traj)')
     ap.add_argument('--trajectory-slots', type=int, default=64)
     ap.add_argument('--no-facade-leg', action='store_true', help='skip config.facade_n1 (BASELINE config 1: one game behind the dict API)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write what the headline's last step handed back (obs, mask, reward, done, player; fobs with "
+                         "--full-obs) as DIR/<name>.npy in float32, over a fixed seeded sample of the envs (DIR/env_ids.npy, float64): at "
+                         "most 64 MB, identical inputs from run to run, so that two builds can be compared output for output (rank 0's games)")
+    ap.add_argument('--details', metavar='FILE', default=None,
+                    help="write the full record of the run (every leg's own figures) to FILE as JSON; the printed line carries the headline "
+                         "and the legs' summary")
     ap.add_argument('--traffic-probe', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--dry-run', action='store_true',
                     help="launcher self-test on CPU: gloo, stub env, no measurement (value is null)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs a real run (the --dry-run stub computes nothing)")
     if args.envs is None:
         # the SAME per-GPU workload on any number of GPUs (BASELINE config 2 on every GPU): `value` over --gpus 1 / 2 / 4 / 8 is a weak-scaling
         # curve of one workload.  BASELINE config 5 (262,144 games per GPU, 2,097,152 on 8) is config.scaling_legs[0] of every multi-GPU
@@ -835,6 +848,57 @@ def line_summary(out):
     return s
 
 
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 0x5EED
+DUMP_MAX_SAMPLE = 1024
+
+
+def dump_outputs(env, out_dir):
+    """--dump-outputs: what the timed path's last step handed back (VecStrategoEnv.rollout_steps returns obs, mask, reward, done, player;
+    fobs with BOTH_OBSERVATIONS) written as out_dir/<name>.npy in float32, over a fixed sample of the envs drawn with a fixed seed
+    (out_dir/env_ids.npy, float64, sorted; every env when the batch fits).  Outside the timed region; reads only, changes no env state."""
+    import numpy as np
+    import torch
+    n = env.num_envs
+    arrays = [('obs', env.obs), ('mask', env.mask), ('reward', env.reward), ('done', env.done), ('player', env.player)]
+    if env.fobs is not None:
+        arrays.append(('fobs', env.fobs))
+    per_env = sum(4 * (t[0].numel() if t.dim() > 1 else 1) for _, t in arrays) + 8
+    k = min(n, DUMP_MAX_SAMPLE, DUMP_MAX_BYTES // per_env)
+    ids = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    idx = torch.from_numpy(ids).to(env.device)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, 'env_ids.npy'), ids.astype(np.float64))
+    for name, t in arrays:
+        np.save(os.path.join(out_dir, name + '.npy'), t[idx].cpu().numpy().astype(np.float32))
+
+
+EXTRA_LEGS = ("other_workloads", "consumer_in_loop", "compact_outputs", "trajectory", "as_it_comes", "facade_n1")
+EXTRA_LEG_FIGURES = ("config3_standard_262144", "config4_micro_65536", "both_observations_65536", "config5_per_gpu_size_barrage_262144",
+                     "trajectory", "compact_outputs", "as_it_comes", "consumer_in_loop", "facade_n1")
+
+
+def result_line(out):
+    """The printed line: the full record without the extra legs' own records (config.other_workloads ... facade_n1; their figures stay in
+    summary_at_the_end_of_the_line, which keeps only those), the store probe's sweeps and the roofline's prose -- a few KB, so that a
+    reader that keeps only the tail of the output still gets the whole line.  --details FILE has everything."""
+    line = dict(out)
+    if isinstance(out.get("config"), dict):
+        line["config"] = {k: v for k, v in out["config"].items() if k not in EXTRA_LEGS}
+    if isinstance(out.get("roofline"), dict):
+        line["roofline"] = {k: v for k, v in out["roofline"].items() if k not in ("store_probe", "frac_basis", "frac_dram_basis")}
+    s = out.get("summary_at_the_end_of_the_line")
+    if isinstance(s, dict):
+        s = {k: s[k] for k in EXTRA_LEG_FIGURES if k in s}
+        traj = s.get("trajectory")
+        ring = (traj or {}).get("ring_of_separately_placed_sets")
+        if ring and isinstance(ring.get("same_memory"), dict):
+            traj = dict(traj, ring_of_separately_placed_sets=dict(ring, same_memory={k: v for k, v in ring["same_memory"].items() if k != "what"}))
+            s["trajectory"] = traj
+        line["summary_at_the_end_of_the_line"] = s
+    return line
+
+
 def run_rank(args):      # noqa: C901
     global DRY_RUN, SETTLE_SECONDS
     dry = DRY_RUN = args.dry_run
@@ -885,6 +949,8 @@ def run_rank(args):      # noqa: C901
     # outside the timed region: the envs that were just timed against the CPU oracle, and the sharding-independent checksum
     checked = verify_against_oracle(env, args.version, args.verify_envs, both=args.full_obs) if (args.verify_envs and not dry) else 0
     verified_steps = env.bench_steps_played
+    if args.dump_outputs and rk.rank == 0:
+        dump_outputs(env, args.dump_outputs)
     _, (checked, checksum, covered) = rk.reduce([], [checked, outputs_checksum(env) if not dry else 0, n])
     in_place, two_chains, no_settle = None, None, None
     per_step = b_min(v, args.full_obs, rec_bytes, fused)
@@ -1058,7 +1124,10 @@ def run_rank(args):      # noqa: C901
         else:
             out["cpu_baseline"] = None
         out["summary_at_the_end_of_the_line"] = line_summary(out)
-        print(json.dumps(out), flush=True)
+        if args.details:
+            with open(args.details, 'w') as f:
+                json.dump(out, f)
+        print(json.dumps(result_line(out)), flush=True)
     rk.close()
 
 

@@ -127,7 +127,7 @@ struct sgx_env {
     int multi_step_attr;         // lane_steps_kernel's dynamic-LDS attribute has been raised
     int last_kind;               // sgx_last_launch_kind: which kernel the last step / observe launch of this handle was
     int multi_step_wave;         // SGX_MULTI_STEP_WAVE: the multi-step launch of the wave-per-game kernels (steps_kernel) too
-    int steps_barrier;           // sgx_set_steps_barrier / SGX_STEPS_BARRIER: -1 auto (long rings that render float32 observations: launch_wave_steps), 0 never, 1 always
+    int steps_barrier;           // sgx_set_steps_barrier / SGX_STEPS_BARRIER: -1 auto (long rings that render float32 observations: steps_kernel), 0 never, 1 always
     int half_wave;               // SGX_HALF_WAVE: launches without an observation play two games per wave where the board allows it (Geo<R, C, 2>)
     // sgx_step_ring with more output sets than fit the kernel arguments: the sets' pointers in a device table (filled through a pinned host
     // copy; the event guards the staging buffer against being rewritten before the previous upload has run)
@@ -163,14 +163,19 @@ bool supported_geometry(int r, int c) {
     return false;
 }
 
-#define SGX_DISPATCH_ONE(CALL, R, C) if (!done_ && r_ == (R) && c_ == (C)) { CALL(R, C); done_ = true; }
-#define DISPATCH_GEOMETRY(h, CALL)                                                     \
-    do {                                                                               \
-        const int r_ = (h)->cfg.rows, c_ = (h)->cfg.cols;                              \
-        bool done_ = false;                                                            \
-        SGX_ALL_GEOMETRIES(SGX_DISPATCH_ONE, CALL)                                     \
-        if (!done_) return fail(SGX_EINVAL, "unsupported board size%s");               \
-    } while (0)
+template <int N> using int_c = std::integral_constant<int, N>;
+template <bool B> using bool_c = std::integral_constant<bool, B>;
+
+// The one place a board size becomes template arguments: calls f(int_c<R>, int_c<C>) for the handle's board (the callee reads them as
+// decltype(r)::value); a launch that only some boards have sits under `if constexpr` inside f.
+template <class F>
+int for_geometry(const sgx_env *h, F &&f) {
+    const int r = h->cfg.rows, c = h->cfg.cols;
+#define SGX_DISPATCH_ONE(A, R, C) if (r == (R) && c == (C)) { f(int_c<(R)>(), int_c<(C)>()); return SGX_OK; }
+    SGX_ALL_GEOMETRIES(SGX_DISPATCH_ONE, _)
+#undef SGX_DISPATCH_ONE
+    return fail(SGX_EINVAL, "unsupported board size%s");
+}
 
 // bytes of one game's compact observation record (SGX_STEP_COMPACT_OBS): 4-bit codes padded to 16 B, a 16-byte header, then room for
 // every entry that can be without a code (capture events + the four recent-move pairs) as {uint32 entry, float value}; whole 128-byte lines
@@ -588,24 +593,28 @@ SGX_API int sgx_reset(sgx_env *h, const uint8_t *env_select_dev, const int8_t *p
     rp.select = env_select_dev;
     rp.p1_maps = p1_maps_dev;
     rp.p2_maps = p2_maps_dev;
-#define CALL_RESET(R, C) reset_kernel<R, C><<<(unsigned)h->n_envs, 64, 0, (hipStream_t)stream>>>(rp)
-    DISPATCH_GEOMETRY(h, CALL_RESET);
-#undef CALL_RESET
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            reset_kernel<decltype(r)::value, decltype(c)::value><<<(unsigned)h->n_envs, 64, 0, (hipStream_t)stream>>>(rp);
+        })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
 
-// Observation bytes one launch writes; beyond what the 256 MiB Infinity Cache absorbs the kernel uses non-temporal stores for the
-// lines a wave writes whole (measured crossover between 281 and 316 MB on four board sizes, sgx_obs.h).
-// `sets`: output sets written round-robin (sgx_step_ring): a line is written again only after `sets` launches, so what has to fit the
-// cache for plain stores to pay is the observations of all of them.
-static bool launch_streams_past_cache(const sgx_env *h, const KParams &p, int sets = 1) {
+// Beyond what the 256 MiB Infinity Cache absorbs a launch's kernels use non-temporal stores for the lines a wave writes whole (measured
+// crossover between 281 and 316 MB on four board sizes, sgx_obs.h).
+constexpr int64_t CACHE_FIT_BYTES = (int64_t)300 * 1000 * 1000;
+static bool past_cache(int64_t bytes) { return bytes > CACHE_FIT_BYTES; }
+// non-temporal stores for a launch that writes `bytes`: sgx_set_nt_stores, else by the size
+static int nt_for(const sgx_env *h, int64_t bytes) { return h->nt_mode < 0 ? (past_cache(bytes) ? 1 : 0) : h->nt_mode; }
+
+// float32 observation bytes one launch writes
+static int64_t launch_obs_bytes(const sgx_env *h, const KParams &p) {
     const bool original = (p.io.flags & SGX_STEP_ORIGINAL_CHANNELS) != 0;
     const int64_t cells = (int64_t)h->cfg.rows * h->cfg.cols;
     int64_t bytes = 0;
     if (p.io.obs_dev) bytes += h->n_envs * cells * lut_channels(false, original) * 4;
     if (p.io.fobs_dev) bytes += h->n_envs * cells * lut_channels(true, original) * 4;
-    return bytes * sets > (int64_t)300 * 1000 * 1000;
+    return bytes;
 }
 
 // Workgroup-groups per XCD for `groups` groups of games from the shares w[8] (per mille of the mean share): KParams::xcd_first /
@@ -633,6 +642,29 @@ static void launch_shares(const sgx_env *h, bool streaming, int32_t *w) {
     const int cells = h->cfg.rows * h->cfg.cols;
     const int skew = h->xcd_skew < 0 ? ((streaming && cells >= 64 && cells <= 100) ? SGX_XCD_SKEW_DEFAULT : 0) : h->xcd_skew;
     for (int x = 0; x < 8; ++x) w[x] = (x & 1) ? 1000 - skew : 1000 + skew;
+}
+
+// What every step launch takes from the handle: the SGX_MAP experiment, non-temporal stores and the XCD shares w.  `sets`: output sets
+// written round-robin (sgx_step_ring): a line is written again only after `sets` launches, so what has to fit the cache for plain stores
+// to pay is the observations of all of them.
+static void launch_setup(const sgx_env *h, KParams &p, int sets, int32_t *w) {
+    p.map_mode = h->map_mode; p.map_arg = h->map_arg;
+    const int64_t bytes = launch_obs_bytes(h, p) * sets;
+    p.nt_stores = nt_for(h, bytes);
+    launch_shares(h, past_cache(bytes), w);                   // unequal XCD shares (sgx_layout.h: group_of_block)
+}
+// the grid of a launch that plays `games` games per workgroup (Geo::WPB x Geo::GPW, the lane kernels' 64) over the envs [env_first, n_envs)
+static unsigned grid_for(KParams &p, int64_t games, const int32_t *w) { return shares_for(p, (p.n_envs - p.env_first + games - 1) / games, w); }
+template <class G>
+unsigned geo_grid(KParams &p, const int32_t *w) { return grid_for(p, G::WPB * G::GPW, w); }
+
+// The variant of a wave-per-game launch of observation kind KIND: two games per wave (Geo<R, C, 2>) for the launches without an observation
+// on the boards that allow it (half_wave_ok) unless sgx_set_half_wave / SGX_HALF_WAVE switched it off, else one.  Calls f(int_c<VAR>).
+template <int R, int C, int KIND, class F>
+void with_half_wave(const sgx_env *h, F &&f) {
+    if constexpr (KIND == 8 && half_wave_ok<R, C>())
+        if (h->half_wave) return f(int_c<2>());
+    f(int_c<0>());
 }
 
 // The lane-per-game kernel plays this launch?  (sgx_lane_kernel.h: what it covers; everything else is the wave-per-game kernel.)
@@ -737,155 +769,95 @@ static int upload_ring_table(sgx_env *h, const OutSets &sets, hipStream_t stream
 
 // sgx_step_n / sgx_step_ring / sgx_step_traj on boards of at most 16 cells: the steps in launches of lane_steps_kernel (sgx_lane_kernel.h)
 // where the call is eligible -- the lane kernel's conditions for every output set, flat perspective actions, observations wanted.
-// *launched tells.
-static int launch_lane_steps(sgx_env *h, const KParams &p_in, const OutSets &sets, int32_t first_set, int32_t n_steps, void *stream, bool *launched) {
-    *launched = false;
-    const int32_t n_sets = sets.n_sets;
-    if (n_steps < 2 || h->lane_mode == 0 || h->no_multi_step) return SGX_OK;
-    const bool table = !sets.strided && n_sets > KSTEP_MAX_SETS;        // more separate sets than the kernel arguments hold: a device table
-    KParams p = p_in;
-    p.mode = 0;
-    p.io = sets.ios[sets.strided ? 0 : first_set];
-    if (!p.io.obs_dev || (p.io.flags & (SGX_STEP_ACTIONS_1D | SGX_STEP_ACTIONS_POSITIONS))) return SGX_OK;
-    StepsParams sp;
-    memset(&sp, 0, sizeof(sp));
+// (p.io: the outputs of the call's first set.)
+static bool lane_steps_ok(const sgx_env *h, const KParams &p, const OutSets &sets) {
+    if (h->lane_mode == 0 || !p.io.obs_dev || (p.io.flags & (SGX_STEP_ACTIONS_1D | SGX_STEP_ACTIONS_POSITIONS))) return false;
     if (sets.strided) {
         const bool full = p.io.fobs_dev || p.io.final_fobs_dev, original = (p.io.flags & SGX_STEP_ORIGINAL_CHANNELS) != 0;
         // every slot as aligned as slot 0 (the kernel's 16-byte stores), per-slot results as aligned as the results of slot 0
-        if (!lane_eligible(h, p, full, original, true) || ((sets.obs_b | sets.mask_b) & 15) || (p.traj_res_envs & 1)) return SGX_OK;
-        sp.strided = 1;
-        sp.obs_slot_bytes = sets.obs_b;
-        sp.mask_slot_bytes = sets.mask_b;
-        sp.obs[0] = p.io.obs_dev;
-        sp.mask[0] = p.io.mask_dev;
-    } else
-        for (int32_t k = 0; k < n_sets; ++k) {
-            KParams pk = p;
-            pk.io = sets.ios[k];
-            const bool full = pk.io.fobs_dev || pk.io.final_fobs_dev, original = (pk.io.flags & SGX_STEP_ORIGINAL_CHANNELS) != 0;
-            if (!pk.io.obs_dev || !lane_eligible(h, pk, full, original, true)) return SGX_OK;
-            // everything but the observation / mask tensors is shared by the sets (the kernel writes the results through set first_set's pointers)
-            if (pk.io.reward_dev != p.io.reward_dev || pk.io.done_dev != p.io.done_dev || pk.io.player_dev != p.io.player_dev ||
-                pk.io.invalid_action_dev != p.io.invalid_action_dev || pk.io.ending_invalid_dev != p.io.ending_invalid_dev) return SGX_OK;
-            if (!table) {
-                sp.obs[k] = pk.io.obs_dev;
-                sp.mask[k] = pk.io.mask_dev;
-            }
-        }
-    if (int rc = check_step_io(h, p)) return rc;
-    if (table) {
-        void **tab = nullptr;
-        if (int rc = upload_ring_table(h, sets, (hipStream_t)stream, &tab)) return rc;
-        sp.strided = 2;
-        sp.obs_tab = reinterpret_cast<float *const *>(tab);
-        sp.mask_tab = reinterpret_cast<uint8_t *const *>(tab + 2 * n_sets);
+        return lane_eligible(h, p, full, original, true) && !((sets.obs_b | sets.mask_b) & 15) && !(p.traj_res_envs & 1);
     }
-    p.map_mode = h->map_mode; p.map_arg = h->map_arg;
-    const bool streaming = launch_streams_past_cache(h, p, n_sets);
-    p.nt_stores = h->nt_mode < 0 ? (streaming ? 1 : 0) : h->nt_mode;
-    int32_t skew[8];
-    launch_shares(h, streaming, skew);
-    sp.n_sets = n_sets;
-    for (int32_t done = 0; done < n_steps; ) {
-        const int32_t now = n_steps - done > SGX_STEPS_MAX_PER_LAUNCH ? SGX_STEPS_MAX_PER_LAUNCH : n_steps - done;
-        const int32_t set = (int32_t)(((int64_t)first_set + done) % n_sets);
-        if (now < 2) {                                                      // a single step left over: the ordinary launch
-            if (int rc = launch_set_step(h, p_in, sets, set, stream)) return rc;
-            done += now;
-            continue;
-        }
-        sp.n_steps = now; sp.first_set = set;
-        bool ok = false;
-#define CALL_LANE_STEPS(R, C)                                                                                      \
-    do {                                                                                                           \
-        if constexpr (lane_geometry<Geo<R, C>>()) {                                                                \
-            const unsigned grid = shares_for(p, (p.n_envs - p.env_first + 63) / 64, skew);                         \
-            const size_t dyn = 2 * 64 * (size_t)(p.rec_bytes + 16);                                                \
-            if (dyn + sizeof(StepsLds<Geo<R, C>>) > 64 * 1024 && !h->multi_step_attr) {                            \
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(&lane_steps_kernel<R, C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) { \
-                    (void)hipGetLastError();                                                                       \
-                    h->no_multi_step = 1;                  /* this runtime keeps workgroups to 64 KiB: per-step launches */ \
-                    break;                                                                                         \
-                }                                                                                                  \
-                h->multi_step_attr = 1;                                                                            \
-            }                                                                                                      \
-            sp.k = p;                                                                                              \
-            lane_steps_kernel<R, C><<<grid, 64 * (1 + KSTEP_EMITTERS), dyn, (hipStream_t)stream>>>(sp);            \
-            ok = true;                                                                                             \
-        }                                                                                                          \
-    } while (0)
-        DISPATCH_GEOMETRY(h, CALL_LANE_STEPS);
-#undef CALL_LANE_STEPS
-        if (!ok) {
-            if (done == 0) return SGX_OK;                                   // (not this board / this runtime: nothing was launched)
-            return fail(SGX_EDEVICE, "lane_steps_kernel became unavailable in the middle of a call%s");
-        }
-        HIP_TRY(hipGetLastError());
-        done += now;
+    for (int32_t k = 0; k < sets.n_sets; ++k) {
+        KParams pk = p;
+        pk.io = sets.ios[k];
+        const bool full = pk.io.fobs_dev || pk.io.final_fobs_dev, original = (pk.io.flags & SGX_STEP_ORIGINAL_CHANNELS) != 0;
+        if (!pk.io.obs_dev || !lane_eligible(h, pk, full, original, true)) return false;
     }
-    *launched = true;
-    h->last_kind = SGX_LAUNCH_MULTI_STEP;
-    return SGX_OK;
+    return true;
 }
 
 // The same for the wave-per-game kernels (steps_kernel, sgx_step.h): the steps of an sgx_step_n / sgx_step_ring / sgx_step_traj call in launches
 // of up to 256 steps -- the games' boards stay in LDS, the record travels once per launch, the waves drift out of phase -- for the 67-channel
-// 'extended' kind, BOTH observations, compact outputs and launches without an observation; perspective actions and masks; at most 8
+// 'extended' kind, BOTH observations, compact outputs and launches without an observation; perspective actions and masks; any number of
 // separate output sets, or any number of slots of a trajectory buffer.
-static int launch_wave_steps(sgx_env *h, const KParams &p_in, const OutSets &sets, int32_t first_set, int32_t n_steps, void *stream, bool *launched) {
-    *launched = false;
-    const int32_t n_sets = sets.n_sets;
-    if (n_steps < 2 || h->no_multi_step || !h->multi_step_wave || h->map_mode != 0) return SGX_OK;
-    const bool table = !sets.strided && n_sets > WSTEPS_MAX_SETS;       // more separate sets than the kernel arguments hold: a device table
-    KParams p = p_in;
-    p.mode = 0;
-    p.io = sets.ios[sets.strided ? 0 : first_set];
+static bool wave_steps_ok(const sgx_env *h, const KParams &p, const OutSets &sets) {
     const sgx_step_io &io0 = p.io;
-    if (io0.flags & (SGX_STEP_ACTIONS_1D | SGX_STEP_ACTIONS_POSITIONS | SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS | SGX_STEP_ORIGINAL_CHANNELS)) return SGX_OK;
+    if (!h->multi_step_wave || h->map_mode != 0) return false;
+    if (io0.flags & (SGX_STEP_ACTIONS_1D | SGX_STEP_ACTIONS_POSITIONS | SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS | SGX_STEP_ORIGINAL_CHANNELS)) return false;
     const bool compact = (io0.flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) != 0;
     const bool full = io0.fobs_dev || io0.final_fobs_dev;
     const bool no_obs = !io0.obs_dev && !io0.fobs_dev && !io0.final_obs_dev && !io0.final_fobs_dev && !compact;
-    if (compact && (full || io0.final_obs_dev)) return SGX_OK;             // (launch_step refuses these: let it say so)
-    if (compact && ((reinterpret_cast<uintptr_t>(io0.obs_dev) | reinterpret_cast<uintptr_t>(io0.mask_dev)) & 15)) return SGX_OK;
+    auto misaligned = [](const sgx_step_io &io) { return ((reinterpret_cast<uintptr_t>(io.obs_dev) | reinterpret_cast<uintptr_t>(io.mask_dev)) & 15) != 0; };
+    if (compact && (full || io0.final_obs_dev)) return false;             // (launch_step refuses these: let it say so)
+    if (compact && misaligned(io0)) return false;
     // Logic-only rollouts (no observation pointer) on 3x4: the lane-per-game kernel, one launch per step, stays ahead of this kernel's multi-step
     // launch there -- 65,536 Micro games mask only 14.9 against 18.2 us per step, no outputs 13.4 against 15.7; 262,144 games 44 against 65 --
     // while on 4x4 the multi-step launch wins (Tiny 15.0 against 17.5 us, 262,144 games 56 against 74: tools/noobs_small_ab.py,
     // profiles/r06_noobs_small_ab.log)
-    if (no_obs && h->cfg.rows * h->cfg.cols <= 12 && lane_eligible(h, p, false, false)) return SGX_OK;
-    WaveStepsParams sp;
-    memset(&sp, 0, sizeof(sp));
-    if (sets.strided) {
-        if (compact && ((sets.obs_b | sets.mask_b) & 15)) return SGX_OK;
-        sp.strided = 1;
-        sp.obs_slot_bytes = sets.obs_b; sp.fobs_slot_bytes = sets.fobs_b; sp.mask_slot_bytes = sets.mask_b;
-        sp.obs[0] = io0.obs_dev; sp.fobs[0] = io0.fobs_dev; sp.mask[0] = io0.mask_dev;
-    } else
-        for (int32_t k = 0; k < n_sets; ++k) {
-            const sgx_step_io &io = sets.ios[k];
-            // the sets differ in their output tensors only, and every set has the tensors the first one has
-            if (io.reward_dev != io0.reward_dev || io.done_dev != io0.done_dev || io.player_dev != io0.player_dev || io.invalid_action_dev != io0.invalid_action_dev ||
-                io.ending_invalid_dev != io0.ending_invalid_dev || io.final_obs_dev != io0.final_obs_dev || io.final_fobs_dev != io0.final_fobs_dev ||
-                (io.obs_dev == nullptr) != (io0.obs_dev == nullptr) || (io.fobs_dev == nullptr) != (io0.fobs_dev == nullptr) ||
-                (io.mask_dev == nullptr) != (io0.mask_dev == nullptr)) return SGX_OK;
-            if (compact && ((reinterpret_cast<uintptr_t>(io.obs_dev) | reinterpret_cast<uintptr_t>(io.mask_dev)) & 15)) return SGX_OK;
-            if (!table) { sp.obs[k] = io.obs_dev; sp.fobs[k] = io.fobs_dev; sp.mask[k] = io.mask_dev; }
-        }
-    if (int rc = check_step_io(h, p)) return rc;
-    if (table) {
-        void **tab = nullptr;
-        if (int rc = upload_ring_table(h, sets, (hipStream_t)stream, &tab)) return rc;
-        sp.strided = 2;
-        sp.obs_tab = reinterpret_cast<float *const *>(tab);
-        sp.fobs_tab = reinterpret_cast<float *const *>(tab + n_sets);
-        sp.mask_tab = reinterpret_cast<uint8_t *const *>(tab + 2 * n_sets);
+    if (no_obs && h->cfg.rows * h->cfg.cols <= 12 && lane_eligible(h, p, false, false)) return false;
+    if (sets.strided) return !(compact && ((sets.obs_b | sets.mask_b) & 15));
+    for (int32_t k = 0; k < sets.n_sets; ++k) {
+        const sgx_step_io &io = sets.ios[k];
+        // every set has the tensors the first one has
+        if (io.final_obs_dev != io0.final_obs_dev || io.final_fobs_dev != io0.final_fobs_dev || (io.obs_dev == nullptr) != (io0.obs_dev == nullptr) ||
+            (io.fobs_dev == nullptr) != (io0.fobs_dev == nullptr) || (io.mask_dev == nullptr) != (io0.mask_dev == nullptr)) return false;
+        if (compact && misaligned(io)) return false;
     }
-    p.map_mode = 0; p.map_arg = h->map_arg;
-    const bool streaming = launch_streams_past_cache(h, p, n_sets);
-    p.nt_stores = h->nt_mode < 0 ? (streaming ? 1 : 0) : h->nt_mode;
-    int32_t skew[8];
-    launch_shares(h, streaming, skew);
-    const int kind = compact ? 4 : no_obs ? 8 : full ? 1 : 0;
-    sp.n_sets = n_sets;
+    return true;
+}
+
+// Separate output sets differ in their observation / mask tensors only: the multi-step kernels write the per-step results through the first
+// set's pointers.
+static bool sets_share_results(const OutSets &sets, const sgx_step_io &io0) {
+    if (sets.strided) return true;
+    for (int32_t k = 0; k < sets.n_sets; ++k) {
+        const sgx_step_io &io = sets.ios[k];
+        if (io.reward_dev != io0.reward_dev || io.done_dev != io0.done_dev || io.player_dev != io0.player_dev || io.invalid_action_dev != io0.invalid_action_dev ||
+            io.ending_invalid_dev != io0.ending_invalid_dev) return false;
+    }
+    return true;
+}
+
+// One launch of lane_steps_kernel: sp.n_steps steps from set sp.first_set.  *ok = false: this runtime keeps workgroups to 64 KiB of LDS
+// (nothing was launched; the handle plays per-step launches from now on).
+static int steps_launch(sgx_env *h, StepsParams &sp, KParams &p, const int32_t *w, hipStream_t stream, bool *ok) {
+    *ok = false;
+    return for_geometry(h, [&](auto r, auto c) {
+        constexpr int R = decltype(r)::value, C = decltype(c)::value;
+        if constexpr (lane_geometry<Geo<R, C>>()) {
+            const unsigned grid = grid_for(p, 64, w);
+            const size_t dyn = 2 * 64 * (size_t)(p.rec_bytes + 16);
+            if (dyn + sizeof(StepsLds<Geo<R, C>>) > 64 * 1024 && !h->multi_step_attr) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void *>(&lane_steps_kernel<R, C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
+                    (void)hipGetLastError();
+                    h->no_multi_step = 1;
+                    return;
+                }
+                h->multi_step_attr = 1;
+            }
+            sp.k = p;
+            lane_steps_kernel<R, C><<<grid, 64 * (1 + KSTEP_EMITTERS), dyn, stream>>>(sp);
+            *ok = true;
+        }
+    });
+}
+
+// One launch of steps_kernel.
+static int steps_launch(sgx_env *h, WaveStepsParams &sp, KParams &p, const int32_t *w, hipStream_t stream, bool *ok) {
+    const sgx_step_io &io = p.io;
+    const bool compact = (io.flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) != 0;
+    const bool no_obs = !io.obs_dev && !io.fobs_dev && !io.final_obs_dev && !io.final_fobs_dev && !compact;
+    const int kind = compact ? 4 : no_obs ? 8 : (io.fobs_dev || io.final_fobs_dev) ? 1 : 0;
     // A barrier per step between the waves of a workgroup: on a long ring or trajectory buffer (the resident waves cycle through more sets than
     // the address translation caches hold pages for: DESIGN.md section 4.4) the workgroup's games then write one set at a time.  In-process A/B
     // of the two modes, drifting -> in step (tools/barrier_footprint_ab.py; profiles/r06_barrier_boards_ab.log, r06_barrier_footprint_ab.log):
@@ -899,67 +871,110 @@ static int launch_wave_steps(sgx_env *h, const KParams &p_in, const OutSets &set
     // so: float32 observations, one game per wave (36 .. 225 cells), from 9 sets / slots on 10x10 and from 16 elsewhere.  Never on a launch with a
     // partly empty last workgroup (its missing waves have left the kernel).
     const int cells = h->cfg.rows * h->cfg.cols;
-    const bool pays = (kind == 0 || kind == 1) && cells >= 36 && cells <= 225 && n_sets >= (cells == 100 ? WSTEPS_MAX_SETS + 1 : 16);
+    const bool pays = (kind == 0 || kind == 1) && cells >= 36 && cells <= 225 && sp.n_sets >= (cells == 100 ? WSTEPS_MAX_SETS + 1 : 16);
     const bool want_barrier = h->steps_barrier > 0 || (h->steps_barrier < 0 && pays);
+    *ok = true;
+    return for_geometry(h, [&](auto r, auto c) {
+        constexpr int R = decltype(r)::value, C = decltype(c)::value;
+        auto launch = [&](auto kind_c) {
+            constexpr int KIND = decltype(kind_c)::value;
+            with_half_wave<R, C, KIND>(h, [&](auto var) {
+                constexpr int VAR = decltype(var)::value;
+                using G = Geo<R, C, VAR>;
+                const unsigned grid = geo_grid<G>(p, w);
+                sp.k = p;
+                sp.barrier = want_barrier && (p.n_envs - p.env_first) % (G::WPB * G::GPW) == 0;
+                steps_kernel<R, C, KIND, VAR><<<grid, 64 * G::WPB, 0, stream>>>(sp);
+            });
+        };
+        if (kind == 0) launch(int_c<0>());
+        else if (kind == 1) launch(int_c<1>());
+        else if (kind == 4) launch(int_c<4>());
+        else launch(int_c<8>());
+    });
+}
+
+// All n_steps of a rollout call -- output sets first, first + 1, ... round-robin -- in the multi-step launches of one kernel family (SP =
+// StepsParams: lane_steps_kernel, WaveStepsParams: steps_kernel) where the call is eligible for it; *launched tells.
+template <class SP>
+static int multi_step(sgx_env *h, const KParams &p_in, const OutSets &sets, int32_t first, int32_t n_steps, void *stream, bool *launched) {
+    constexpr bool lane = std::is_same<SP, StepsParams>::value;
+    *launched = false;
+    const int32_t n_sets = sets.n_sets;
+    KParams p = p_in;
+    p.mode = 0;
+    p.io = sets.ios[sets.strided ? 0 : first];
+    if (n_steps < 2 || h->no_multi_step || !(lane ? lane_steps_ok(h, p, sets) : wave_steps_ok(h, p, sets)) || !sets_share_results(sets, p.io)) return SGX_OK;
+    if (int rc = check_step_io(h, p)) return rc;
+    SP sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.n_sets = n_sets;
+    if (sets.strided) {
+        sp.strided = 1;
+        sp.obs_slot_bytes = sets.obs_b; sp.mask_slot_bytes = sets.mask_b;
+        sp.obs[0] = p.io.obs_dev; sp.mask[0] = p.io.mask_dev;
+        if constexpr (!lane) { sp.fobs_slot_bytes = sets.fobs_b; sp.fobs[0] = p.io.fobs_dev; }
+    } else if (n_sets > (int32_t)std::extent<decltype(sp.obs)>::value) {      // more separate sets than the kernel arguments hold: a device table
+        void **tab = nullptr;
+        if (int rc = upload_ring_table(h, sets, (hipStream_t)stream, &tab)) return rc;
+        sp.strided = 2;
+        sp.obs_tab = reinterpret_cast<float *const *>(tab);
+        sp.mask_tab = reinterpret_cast<uint8_t *const *>(tab + 2 * n_sets);
+        if constexpr (!lane) sp.fobs_tab = reinterpret_cast<float *const *>(tab + n_sets);
+    } else
+        for (int32_t k = 0; k < n_sets; ++k) {
+            sp.obs[k] = sets.ios[k].obs_dev; sp.mask[k] = sets.ios[k].mask_dev;
+            if constexpr (!lane) sp.fobs[k] = sets.ios[k].fobs_dev;
+        }
+    int32_t w[8];
+    launch_setup(h, p, n_sets, w);
     for (int32_t done = 0; done < n_steps; ) {
         const int32_t now = n_steps - done > SGX_STEPS_MAX_PER_LAUNCH ? SGX_STEPS_MAX_PER_LAUNCH : n_steps - done;
-        const int32_t set = (int32_t)(((int64_t)first_set + done) % n_sets);
+        const int32_t set = (int32_t)(((int64_t)first + done) % n_sets);
         if (now < 2) {                                                      // a single step left over: the ordinary launch
             if (int rc = launch_set_step(h, p_in, sets, set, stream)) return rc;
-            done += now;
-            continue;
+        } else {
+            sp.n_steps = now; sp.first_set = set;
+            bool ok = false;
+            if (int rc = steps_launch(h, sp, p, w, (hipStream_t)stream, &ok)) return rc;
+            if (!ok) {
+                if (done == 0) return SGX_OK;                               // (not this runtime: nothing was launched)
+                return fail(SGX_EDEVICE, "lane_steps_kernel became unavailable in the middle of a call%s");
+            }
+            HIP_TRY(hipGetLastError());
         }
-        sp.n_steps = now;
-        sp.first_set = set;
-#define CALL_WSTEPS_K(R, C, KIND)                                                                          \
-    do {                                                                                                   \
-        using G_ = Geo<R, C>;                                                                              \
-        const unsigned grid = shares_for(p, (p.n_envs - p.env_first + G_::WPB * G_::GPW - 1) / (G_::WPB * G_::GPW), skew); \
-        sp.k = p;                                                                                          \
-        sp.barrier = want_barrier && (p.n_envs - p.env_first) % (G_::WPB * G_::GPW) == 0;                  \
-        steps_kernel<R, C, KIND><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(sp);                      \
-    } while (0)
-#define CALL_WSTEPS(R, C)                                                                                  \
-    do {                                                                                                   \
-        if (kind == 0) CALL_WSTEPS_K(R, C, 0);                                                             \
-        else if (kind == 1) CALL_WSTEPS_K(R, C, 1);                                                        \
-        else {                                                                                             \
-            bool half_ = false;                                                                            \
-            if constexpr (half_wave_ok<R, C>()) {                                                          \
-                if (h->half_wave && kind == 8) {             /* two games per wave (Geo<R, C, 2>) */        \
-                    using H_ = Geo<R, C, 2>;                                                               \
-                    const unsigned grid = shares_for(p, (p.n_envs - p.env_first + H_::WPB * H_::GPW - 1) / (H_::WPB * H_::GPW), skew); \
-                    sp.k = p;                                                                              \
-                    sp.barrier = want_barrier && (p.n_envs - p.env_first) % (H_::WPB * H_::GPW) == 0;      \
-                    steps_kernel<R, C, 8, 2><<<grid, 64 * H_::WPB, 0, (hipStream_t)stream>>>(sp);           \
-                    half_ = true;                                                                          \
-                }                                                                                          \
-            }                                                                                              \
-            if (!half_) { if (kind == 4) CALL_WSTEPS_K(R, C, 4); else CALL_WSTEPS_K(R, C, 8); }            \
-        }                                                                                                  \
-    } while (0)
-        DISPATCH_GEOMETRY(h, CALL_WSTEPS);
-#undef CALL_WSTEPS
-#undef CALL_WSTEPS_K
-        HIP_TRY(hipGetLastError());
         done += now;
     }
     *launched = true;
-    h->last_kind = SGX_LAUNCH_MULTI_STEP_WAVE;
+    h->last_kind = lane ? SGX_LAUNCH_MULTI_STEP : SGX_LAUNCH_MULTI_STEP_WAVE;
+    return SGX_OK;
+}
+
+// The multi-step launch of a rollout call: the lane-per-game kernel's where the call is eligible for it, else the wave-per-game kernels'.
+static int multi_steps(sgx_env *h, const KParams &p, const OutSets &sets, int32_t first, int32_t n_steps, void *stream, bool *launched) {
+    if (int rc = multi_step<StepsParams>(h, p, sets, first, n_steps, stream, launched)) return rc;
+    if (*launched) return SGX_OK;
+    return multi_step<WaveStepsParams>(h, p, sets, first, n_steps, stream, launched);
+}
+
+// The steps of sgx_step_n / sgx_step_ring / sgx_step_traj: a multi-step launch, else one launch per step.
+static int play_steps(sgx_env *h, const KParams &p, const OutSets &sets, int32_t first, int32_t n_steps, void *stream) {
+    bool launched = false;
+    if (int rc = multi_steps(h, p, sets, first, n_steps, stream, &launched)) return rc;
+    for (int32_t i = 0; i < n_steps && !launched; ++i)
+        if (int rc = launch_set_step(h, p, sets, (int32_t)(((int64_t)first + i) % sets.n_sets), stream)) return rc;
     return SGX_OK;
 }
 
 static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_sets) {
     KParams p = p_in;
-    if (p.mode == 0 && p.io.auto_reset)
-        if (int rc = check_random_setups(h)) return rc;
-    p.map_mode = h->map_mode; p.map_arg = h->map_arg;
-    const bool streaming = launch_streams_past_cache(h, p, ring_sets);
-    p.nt_stores = h->nt_mode < 0 ? (streaming ? 1 : 0) : h->nt_mode;
-    int32_t skew[8];                     // unequal XCD shares (sgx_layout.h: group_of_block)
-    launch_shares(h, streaming, skew);
+    if (int rc = check_step_io(h, p)) return rc;
+    int32_t w[8];
+    launch_setup(h, p, ring_sets, w);
+    const hipStream_t st = (hipStream_t)stream;
     const bool full = p.io.fobs_dev || p.io.final_fobs_dev, original = (p.io.flags & SGX_STEP_ORIGINAL_CHANNELS) != 0;
-    if (p.io.flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) {
+    const bool compact = (p.io.flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) != 0;
+    if (compact) {
         // compact outputs: the 67-channel 'extended' observation as 4-bit codes / the mover's-perspective mask as bits, nothing else
         if (full || original || p.io.final_obs_dev || p.src_boards || (p.io.flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)))
             return fail(SGX_EINVAL, "compact outputs come with the 67-channel partial observation and the perspective mask only (no fobs / final_obs / original channels / state-coordinate masks)%s");
@@ -968,94 +983,47 @@ static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_s
     }
     if (lane_eligible(h, p, full, original)) {
         // boards of at most 16 cells: one game per lane, 64 games per wave (sgx_lane_kernel.h)
-#define CALL_LANE(R, C)                                                                                    \
-    do {                                                                                                   \
-        if constexpr (lane_geometry<Geo<R, C>>()) {                                                        \
-            const unsigned grid = shares_for(p, (p.n_envs - p.env_first + 63) / 64, skew);                 \
-            const size_t dyn = 64 * (size_t)(p.rec_bytes + 16);                                            \
-            if (p.mode) lane_kernel<R, C, true><<<grid, 64, dyn, (hipStream_t)stream>>>(p);                \
-            else lane_kernel<R, C, false><<<grid, 64, dyn, (hipStream_t)stream>>>(p);                      \
-        }                                                                                                  \
-    } while (0)
-        DISPATCH_GEOMETRY(h, CALL_LANE);
-#undef CALL_LANE
+        if (int rc = for_geometry(h, [&](auto r, auto c) {
+                constexpr int R = decltype(r)::value, C = decltype(c)::value;
+                if constexpr (lane_geometry<Geo<R, C>>()) {
+                    const unsigned grid = grid_for(p, 64, w);
+                    const size_t dyn = 64 * (size_t)(p.rec_bytes + 16);
+                    if (p.mode) lane_kernel<R, C, true><<<grid, 64, dyn, st>>>(p);
+                    else lane_kernel<R, C, false><<<grid, 64, dyn, st>>>(p);
+                }
+            })) return rc;
         HIP_TRY(hipGetLastError());
         h->last_kind = SGX_LAUNCH_LANE;
         return SGX_OK;
     }
-#define CALL_STEP_KIND(R, C, KIND)                                                                 \
-    do {                                                                                           \
-        using G_ = Geo<R, C>;                                                                      \
-        const unsigned grid = shares_for(p, (p.n_envs - p.env_first + G_::WPB * G_::GPW - 1) / (G_::WPB * G_::GPW), skew); \
-        if (p.mode) observe_kernel<R, C, KIND><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(p); \
-        else step_kernel<R, C, KIND><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(p);           \
-    } while (0)
-#define CALL_STEP0(R, C) CALL_STEP_KIND(R, C, 0)
-#define CALL_STEP4(R, C) CALL_STEP_KIND(R, C, 4)
-#define CALL_STEP1(R, C) CALL_STEP_KIND(R, C, 1)
-#define CALL_STEP2(R, C) CALL_STEP_KIND(R, C, 2)
-#define CALL_STEP3(R, C) CALL_STEP_KIND(R, C, 3)
-#define CALL_STEP8(R, C)                                                                           \
-    do {                                                                                           \
-        bool half_ = false;                                                                        \
-        if constexpr (half_wave_ok<R, C>()) {                                                      \
-            if (h->half_wave) {                              /* two games per wave (Geo<R, C, 2>) */ \
-                using H_ = Geo<R, C, 2>;                                                           \
-                const unsigned grid = shares_for(p, (p.n_envs - p.env_first + H_::WPB * H_::GPW - 1) / (H_::WPB * H_::GPW), skew); \
-                if (p.mode) observe_kernel<R, C, 8, false, 2><<<grid, 64 * H_::WPB, 0, (hipStream_t)stream>>>(p); \
-                else step_kernel<R, C, 8, false, 2><<<grid, 64 * H_::WPB, 0, (hipStream_t)stream>>>(p); \
-                half_ = true;                                                                      \
-            }                                                                                      \
-        }                                                                                          \
-        if (!half_) CALL_STEP_KIND(R, C, 8);                                                       \
-    } while (0)
     // no observation pointer at all (search expansions, mask-only steps, logic-only rollouts): the kind without observation tables
-    const bool no_obs = !p.io.obs_dev && !p.io.fobs_dev && !p.io.final_obs_dev && !p.io.final_fobs_dev &&
-                        !(p.io.flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK));
-    if ((p.io.flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) || p.src_boards) {
-        if (full || (original && !no_obs)) return fail(SGX_EINVAL, "state-coordinate masks and sgx_expand come with the 67-channel partial observation only%s");
-#define CALL_STEP_MAPPED8(R, C)                                                                    \
-    do {                                                                                           \
-        bool half_ = false;                                                                        \
-        if constexpr (half_wave_ok<R, C>()) {                                                      \
-            if (h->half_wave) {                              /* two games per wave (Geo<R, C, 2>) */ \
-                using H_ = Geo<R, C, 2>;                                                           \
-                const unsigned grid = shares_for(p, (p.n_envs - p.env_first + H_::WPB * H_::GPW - 1) / (H_::WPB * H_::GPW), skew); \
-                if (p.mode) observe_kernel<R, C, 8, true, 2><<<grid, 64 * H_::WPB, 0, (hipStream_t)stream>>>(p); \
-                else step_kernel<R, C, 8, true, 2><<<grid, 64 * H_::WPB, 0, (hipStream_t)stream>>>(p); \
-                half_ = true;                                                                      \
-            }                                                                                      \
-        }                                                                                          \
-        if (half_) break;                                                                          \
-        using G_ = Geo<R, C>;                                                                      \
-        const unsigned grid = shares_for(p, (p.n_envs - p.env_first + G_::WPB * G_::GPW - 1) / (G_::WPB * G_::GPW), skew); \
-        if (p.mode) observe_kernel<R, C, 8, true><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(p);  \
-        else step_kernel<R, C, 8, true><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(p);        \
-    } while (0)
-#define CALL_STEP_MAPPED(R, C)                                                                     \
-    do {                                                                                           \
-        using G_ = Geo<R, C>;                                                                      \
-        const unsigned grid = shares_for(p, (p.n_envs - p.env_first + G_::WPB * G_::GPW - 1) / (G_::WPB * G_::GPW), skew); \
-        if (p.mode) observe_kernel<R, C, 0, true><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(p);  \
-        else step_kernel<R, C, 0, true><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(p);        \
-    } while (0)
-        if (no_obs) DISPATCH_GEOMETRY(h, CALL_STEP_MAPPED8);
-        else DISPATCH_GEOMETRY(h, CALL_STEP_MAPPED);
-#undef CALL_STEP_MAPPED
-#undef CALL_STEP_MAPPED8
-    } else if (p.io.flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) DISPATCH_GEOMETRY(h, CALL_STEP4);
-    else if (no_obs) DISPATCH_GEOMETRY(h, CALL_STEP8);
-    else if (!original && !full) DISPATCH_GEOMETRY(h, CALL_STEP0);
-    else if (!original) DISPATCH_GEOMETRY(h, CALL_STEP1);
-    else if (!full) DISPATCH_GEOMETRY(h, CALL_STEP2);
-    else DISPATCH_GEOMETRY(h, CALL_STEP3);
-#undef CALL_STEP0
-#undef CALL_STEP4
-#undef CALL_STEP1
-#undef CALL_STEP2
-#undef CALL_STEP3
-#undef CALL_STEP8
-#undef CALL_STEP_KIND
+    const bool no_obs = !p.io.obs_dev && !p.io.fobs_dev && !p.io.final_obs_dev && !p.io.final_fobs_dev && !compact;
+    const bool mapped = (p.io.flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) || p.src_boards;
+    if (mapped && (full || (original && !no_obs))) return fail(SGX_EINVAL, "state-coordinate masks and sgx_expand come with the 67-channel partial observation only%s");
+    const int kind = compact ? 4 : no_obs ? 8 : (full ? 1 : 0) + (original ? 2 : 0);      // (sgx_layout.h: ObsKind)
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            auto launch = [&](auto kind_c, auto mapped_c) {
+                constexpr int KIND = decltype(kind_c)::value;
+                constexpr bool MAPPED = decltype(mapped_c)::value;
+                with_half_wave<R, C, KIND>(h, [&](auto var) {
+                    constexpr int VAR = decltype(var)::value;
+                    using G = Geo<R, C, VAR>;
+                    const unsigned grid = geo_grid<G>(p, w);
+                    if (p.mode) observe_kernel<R, C, KIND, MAPPED, VAR><<<grid, 64 * G::WPB, 0, st>>>(p);
+                    else step_kernel<R, C, KIND, MAPPED, VAR><<<grid, 64 * G::WPB, 0, st>>>(p);
+                });
+            };
+            if (mapped) {
+                if (kind == 8) launch(int_c<8>(), bool_c<true>());
+                else launch(int_c<0>(), bool_c<true>());
+            } else if (kind == 0) launch(int_c<0>(), bool_c<false>());
+            else if (kind == 1) launch(int_c<1>(), bool_c<false>());
+            else if (kind == 2) launch(int_c<2>(), bool_c<false>());
+            else if (kind == 3) launch(int_c<3>(), bool_c<false>());
+            else if (kind == 4) launch(int_c<4>(), bool_c<false>());
+            else launch(int_c<8>(), bool_c<false>());
+        })) return rc;
     HIP_TRY(hipGetLastError());
     h->last_kind = SGX_LAUNCH_WAVE;
     return SGX_OK;
@@ -1074,61 +1042,70 @@ SGX_API int sgx_observe(sgx_env *h, float *obs_dev, float *fobs_dev, uint8_t *ma
     return launch_step(h, p, stream);
 }
 
+namespace {
+// Two timing events, destroyed with the pair (err: how creating them went).  time(): the milliseconds `launches` calls of launch() -- an
+// SGX_* code each -- take on `stream`, after one untimed first touch; the first launch's error, else a failed event call as SGX_EDEVICE
+// with the message `what` (a format for the HIP error string).
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t err;
+    EventPair() {
+        err = hipEventCreate(&e0);
+        if (err == hipSuccess) err = hipEventCreate(&e1);
+    }
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    EventPair(const EventPair &) = delete;
+    EventPair &operator=(const EventPair &) = delete;
+    template <class F>
+    int time(hipStream_t stream, int32_t launches, const char *what, float *ms, F &&launch) {
+        if (int rc = launch()) return rc;
+        hipError_t e = hipEventRecord(e0, stream);
+        for (int32_t i = 0; i < launches; ++i)
+            if (int rc = launch()) return rc;
+        if (e == hipSuccess) e = hipEventRecord(e1, stream);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventElapsedTime(ms, e0, e1);
+        return e == hipSuccess ? SGX_OK : fail(SGX_EDEVICE, what, hipGetErrorString(e));
+    }
+};
+}  // namespace
+
 SGX_API int sgx_time_observe(sgx_env *h, float *obs_dev, uint8_t *mask_dev, int32_t launches, void *stream, float *microseconds) {
     if (!h || !microseconds || launches <= 0) return fail(SGX_EINVAL, "bad argument%s");
     SGX_ON_DEVICE(h->device);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    int rc = sgx_observe(h, obs_dev, nullptr, mask_dev, nullptr, 0, stream);       // untimed first touch
-    if (rc == SGX_OK) {
-        hipError_t e = hipEventRecord(e0, (hipStream_t)stream);
-        for (int32_t i = 0; i < launches && rc == SGX_OK; ++i) rc = sgx_observe(h, obs_dev, nullptr, mask_dev, nullptr, 0, stream);
-        if (e == hipSuccess) e = hipEventRecord(e1, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        if (rc == SGX_OK && e != hipSuccess) rc = fail(SGX_EDEVICE, "timing events: %s", hipGetErrorString(e));
-        *microseconds = ms * 1000.f / (float)launches;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
-}
-
-// ---- device-memory probe
-namespace {
-// GB/s of `launches` probe launches over [ptr, ptr + bytes) (one untimed first touch); e0 / e1: scratch events
-int probe_range(void *ptr, int64_t bytes, int32_t launches, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, float *gbps) {
-    const int64_t n_seg = bytes / PROBE_SEG;
-    if (n_seg < 1) return fail(SGX_EINVAL, "sgx_mem_probe: range shorter than one 26 KiB segment%s");
-    const int64_t want = ((int64_t)1 << 30) / PROBE_SEG;                      // at least ~1 GiB of stores per launch
-    const int64_t passes = n_seg >= want ? 1 : (want + n_seg - 1) / n_seg, n_waves = n_seg * passes;
-    const unsigned grid = (unsigned)((((n_waves + 7) / 8) + 7) & ~(int64_t)7);
-    mem_probe_kernel<<<grid, 512, 0, stream>>>((char *)ptr, n_seg, n_waves);
-    HIP_TRY(hipEventRecord(e0, stream));
-    for (int i = 0; i < launches; ++i) mem_probe_kernel<<<grid, 512, 0, stream>>>((char *)ptr, n_seg, n_waves);
-    HIP_TRY(hipEventRecord(e1, stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    HIP_TRY(hipGetLastError());
+    EventPair ev;
+    if (ev.err != hipSuccess) return fail(SGX_EDEVICE, "hipEventCreate: %s", hipGetErrorString(ev.err));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    *gbps = (float)((double)n_waves * PROBE_SEG * launches / (ms * 1e-3) / 1e9);
+    if (int rc = ev.time((hipStream_t)stream, launches, "timing events: %s", &ms,
+                         [&] { return sgx_observe(h, obs_dev, nullptr, mask_dev, nullptr, 0, stream); })) return rc;
+    *microseconds = ms * 1000.f / (float)launches;
     return SGX_OK;
 }
-}  // namespace
 
+// ---- device-memory probe: GB/s of `launches` probe launches over [ptr, ptr + bytes)
 SGX_API int sgx_mem_probe(int device, void *ptr_dev, int64_t bytes, int32_t launches, void *stream, float *gb_per_s) {
     if (!ptr_dev || !gb_per_s || launches <= 0 || bytes <= 0) return fail(SGX_EINVAL, "sgx_mem_probe: bad argument%s");
     if ((reinterpret_cast<uintptr_t>(ptr_dev) & 1023) != 0) return fail(SGX_EINVAL, "sgx_mem_probe: the range must start on a 1 KiB boundary%s");
     SGX_ON_DEVICE(device);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
-    const int rc = probe_range(ptr_dev, bytes, launches, (hipStream_t)stream, e0, e1, gb_per_s);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    const int64_t n_seg = bytes / PROBE_SEG;
+    if (n_seg < 1) return fail(SGX_EINVAL, "sgx_mem_probe: range shorter than one 26 KiB segment%s");
+    EventPair ev;
+    if (ev.err != hipSuccess) return fail(SGX_EDEVICE, "hipEventCreate: %s", hipGetErrorString(ev.err));
+    const int64_t want = ((int64_t)1 << 30) / PROBE_SEG;                      // at least ~1 GiB of stores per launch
+    const int64_t passes = n_seg >= want ? 1 : (want + n_seg - 1) / n_seg, n_waves = n_seg * passes;
+    const unsigned grid = (unsigned)((((n_waves + 7) / 8) + 7) & ~(int64_t)7);
+    const hipStream_t st = (hipStream_t)stream;
+    float ms = 0.f;
+    if (int rc = ev.time(st, launches, "sgx_mem_probe: %s", &ms, [&] {
+            mem_probe_kernel<<<grid, 512, 0, st>>>((char *)ptr_dev, n_seg, n_waves);
+            return SGX_OK;
+        })) return rc;
+    *gb_per_s = (float)((double)n_waves * PROBE_SEG * launches / (ms * 1e-3) / 1e9);
+    return SGX_OK;
 }
 
 // The step kernel's store stream without the game (sgx_mem.h: store_probe_kernel): what the memory takes from exactly this store shape.
@@ -1165,27 +1142,17 @@ SGX_API int sgx_store_probe(int device, void *ptr_dev, int64_t bytes, int32_t se
         else ea = hipFuncSetAttribute(reinterpret_cast<const void *>(&store_probe_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
         if (ea != hipSuccess) return fail(SGX_EDEVICE, "sgx_store_probe: %s", hipGetErrorString(ea));
     }
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0));
-    HIP_TRY(hipEventCreate(&e1));
+    EventPair ev;
+    if (ev.err != hipSuccess) return fail(SGX_EDEVICE, "sgx_store_probe: %s", hipGetErrorString(ev.err));
     static uint32_t salt = 0x5EED5EEDu;
-    auto go = [&]() {
-        salt = salt * 1664525u + 1013904223u;
-        if (payload == 0) store_probe_kernel<0><<<(unsigned)grid, 512, dyn, st>>>((char *)ptr_dev, groups_per_pass, passes, seg_bytes, nt_stores, salt, pace, persistent ? 1 : 0, dwell, ring, ring_bytes);
-        else if (payload == 1) store_probe_kernel<1><<<(unsigned)grid, 512, dyn, st>>>((char *)ptr_dev, groups_per_pass, passes, seg_bytes, nt_stores, salt, pace, persistent ? 1 : 0, dwell, ring, ring_bytes);
-        else store_probe_kernel<2><<<(unsigned)grid, 512, dyn, st>>>((char *)ptr_dev, groups_per_pass, passes, seg_bytes, nt_stores, salt, pace, persistent ? 1 : 0, dwell, ring, ring_bytes);
-    };
-    go();                                                                      // untimed first touch
-    hipError_t e = hipEventRecord(e0, st);
-    for (int32_t i = 0; i < launches; ++i) go();
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = hipEventSynchronize(e1);
-    if (e == hipSuccess) e = hipGetLastError();
     float ms = 0.f;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (e != hipSuccess) return fail(SGX_EDEVICE, "sgx_store_probe: %s", hipGetErrorString(e));
+    if (int rc = ev.time(st, launches, "sgx_store_probe: %s", &ms, [&] {
+            salt = salt * 1664525u + 1013904223u;
+            if (payload == 0) store_probe_kernel<0><<<(unsigned)grid, 512, dyn, st>>>((char *)ptr_dev, groups_per_pass, passes, seg_bytes, nt_stores, salt, pace, persistent ? 1 : 0, dwell, ring, ring_bytes);
+            else if (payload == 1) store_probe_kernel<1><<<(unsigned)grid, 512, dyn, st>>>((char *)ptr_dev, groups_per_pass, passes, seg_bytes, nt_stores, salt, pace, persistent ? 1 : 0, dwell, ring, ring_bytes);
+            else store_probe_kernel<2><<<(unsigned)grid, 512, dyn, st>>>((char *)ptr_dev, groups_per_pass, passes, seg_bytes, nt_stores, salt, pace, persistent ? 1 : 0, dwell, ring, ring_bytes);
+            return SGX_OK;
+        })) return rc;
     *microseconds_per_launch = ms * 1000.f / (float)launches;
     *gb_per_s = (float)((double)n_seg * seg_bytes * passes * dwell * launches / (ms * 1e-3) / 1e9);
     return SGX_OK;
@@ -1198,21 +1165,15 @@ struct TrialCtx {
     sgx_env *h;
     void *stream;
     int32_t flags;
-    hipEvent_t e0, e1;
+    EventPair ev;
 };
 
 // average launch time of 6 sgx_observe launches writing the given buffers (one untimed first touch)
 int time_candidate(TrialCtx &c, float *obs, float *fobs, uint8_t *mask, float *us) {
     const int launches = 6;
-    int rc = sgx_observe(c.h, obs, fobs, mask, nullptr, c.flags, c.stream);
-    if (rc != SGX_OK) return rc;
-    HIP_TRY(hipEventRecord(c.e0, (hipStream_t)c.stream));
-    for (int i = 0; i < launches && rc == SGX_OK; ++i) rc = sgx_observe(c.h, obs, fobs, mask, nullptr, c.flags, c.stream);
-    if (rc != SGX_OK) return rc;
-    HIP_TRY(hipEventRecord(c.e1, (hipStream_t)c.stream));
-    HIP_TRY(hipEventSynchronize(c.e1));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c.e0, c.e1));
+    if (int rc = c.ev.time((hipStream_t)c.stream, launches, "timing events: %s", &ms,
+                           [&] { return sgx_observe(c.h, obs, fobs, mask, nullptr, c.flags, c.stream); })) return rc;
     *us = ms * 1000.f / (float)launches;
     return SGX_OK;
 }
@@ -1307,17 +1268,14 @@ SGX_API int sgx_alloc_outputs(sgx_env *h, int32_t flags, int64_t max_extra_bytes
     out->fobs_bytes = full ? h->n_envs * cells * lut_channels(true, original) * 4 : 0;
     out->mask_bytes = h->n_envs * cells * h->K;
     if (hipMalloc((void **)&out->mask_dev, (size_t)out->mask_bytes) != hipSuccess) return fail(SGX_ENOMEM, "device allocation failed (mask buffer)%s");
-    TrialCtx c{h, stream, flags & SGX_STEP_ORIGINAL_CHANNELS, nullptr, nullptr};
-    int rc = SGX_OK;
-    if (hipEventCreate(&c.e0) != hipSuccess || hipEventCreate(&c.e1) != hipSuccess) rc = fail(SGX_EDEVICE, "hipEventCreate failed%s");
+    TrialCtx c{h, stream, flags & SGX_STEP_ORIGINAL_CHANNELS};
+    int rc = c.ev.err != hipSuccess ? fail(SGX_EDEVICE, "hipEventCreate failed%s") : SGX_OK;
     if (rc == SGX_OK)
         rc = pick_buffer(c, 0, (size_t)out->obs_bytes, nullptr, out->mask_dev, max_extra_bytes, max_trials, &out->obs_dev, out->trial_us,
                          &out->n_trials, &out->peak_extra_bytes);
     if (rc == SGX_OK && full)
         rc = pick_buffer(c, 1, (size_t)out->fobs_bytes, out->obs_dev, out->mask_dev, max_extra_bytes, max_trials, &out->fobs_dev, out->ftrial_us,
                          &out->n_ftrials, &out->peak_extra_bytes);
-    if (c.e0) (void)hipEventDestroy(c.e0);
-    if (c.e1) (void)hipEventDestroy(c.e1);
     if (rc != SGX_OK) {
         const std::string keep = g_last_error;
         (void)sgx_free_outputs(h, out);
@@ -1393,16 +1351,14 @@ int step_single(sgx_env *h, const KParams &p, bool full, hipStream_t stream, boo
         h->sync_count = cnt;
     }
     const uint32_t seq = ++h->sync_seq;
-#define CALL_SINGLE(R, C)                                                                                              \
-    do {                                                                                                               \
-        if constexpr (Geo<R, C>::LPG == 64 && !Geo<R, C>::WIDE && (R * C) % 4 == 0) {                                  \
-            if (full) single_kernel<R, C, 1><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, h->sync_count, h->sync_flag_dev, seq); \
-            else single_kernel<R, C, 0><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, h->sync_count, h->sync_flag_dev, seq);      \
-            *launched = true;                                                                                          \
-        }                                                                                                              \
-    } while (0)
-    DISPATCH_GEOMETRY(h, CALL_SINGLE);
-#undef CALL_SINGLE
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            if constexpr (Geo<R, C>::LPG == 64 && !Geo<R, C>::WIDE && (R * C) % 4 == 0) {
+                if (full) single_kernel<R, C, 1><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, h->sync_count, h->sync_flag_dev, seq);
+                else single_kernel<R, C, 0><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, h->sync_count, h->sync_flag_dev, seq);
+                *launched = true;
+            }
+        })) return rc;
     if (!*launched) return SGX_OK;
     HIP_TRY(hipGetLastError());
     // poll the word the last workgroup writes after a system-scope fence; look at the stream now and then, so that a launch that
@@ -1452,6 +1408,19 @@ SGX_API int sgx_step_sync(sgx_env *h, const sgx_step_io *io, void *stream) {
     return SGX_OK;
 }
 
+// Forks `chains` streams of the handle off the caller's (created on first use, with their join events): each waits for what `stream`
+// holds so far.
+static int fork_chains(sgx_env *h, int chains, hipStream_t stream) {
+    if (!h->chain_fork) HIP_TRY(hipEventCreateWithFlags(&h->chain_fork, hipEventDisableTiming));
+    for (int c = 0; c < chains; ++c) {
+        if (!h->chain_stream[c]) HIP_TRY(hipStreamCreateWithFlags(&h->chain_stream[c], hipStreamNonBlocking));
+        if (!h->chain_join[c]) HIP_TRY(hipEventCreateWithFlags(&h->chain_join[c], hipEventDisableTiming));
+    }
+    HIP_TRY(hipEventRecord(h->chain_fork, stream));
+    for (int c = 0; c < chains; ++c) HIP_TRY(hipStreamWaitEvent(h->chain_stream[c], h->chain_fork, 0));
+    return SGX_OK;
+}
+
 // Joins the chains' streams into the caller's: records every chain's join event and makes `stream` wait for it.  Returns `rc` (the
 // error of the launches, which wins) or the first error of the joining itself.
 static int join_chains(sgx_env *h, int chains, hipStream_t stream, int rc) {
@@ -1476,17 +1445,7 @@ SGX_API int sgx_step_n(sgx_env *h, const sgx_step_io *io, int32_t n_steps, void 
     KParams p = make_params(h);
     p.mode = 0;
     p.io = *io;
-    {   // boards of at most 16 cells: the n_steps in one launch, the games in registers (lane_steps_kernel)
-        bool launched = false;
-        const OutSets one{io, 1, false, 0, 0, 0};
-        if (int rc = launch_lane_steps(h, p, one, 0, n_steps, stream, &launched)) return rc;
-        if (launched) return SGX_OK;
-        if (int rc = launch_wave_steps(h, p, one, 0, n_steps, stream, &launched)) return rc;
-        if (launched) return SGX_OK;
-    }
-    for (int32_t i = 0; i < n_steps; ++i)
-        if (int rc = launch_step(h, p, stream)) return rc;
-    return SGX_OK;
+    return play_steps(h, p, OutSets{io, 1, false, 0, 0, 0}, 0, n_steps, stream);
 }
 
 SGX_API int sgx_step_ring(sgx_env *h, const sgx_step_io *ios, int32_t n_sets, int32_t first_set, int32_t n_steps, void *stream) {
@@ -1501,19 +1460,7 @@ SGX_API int sgx_step_ring(sgx_env *h, const sgx_step_io *ios, int32_t n_sets, in
     SGX_ON_DEVICE(h->device);
     KParams p = make_params(h);
     p.mode = 0;
-    {
-        bool launched = false;
-        const OutSets ring{ios, n_sets, false, 0, 0, 0};
-        if (int rc = launch_lane_steps(h, p, ring, first_set, n_steps, stream, &launched)) return rc;
-        if (launched) return SGX_OK;
-        if (int rc = launch_wave_steps(h, p, ring, first_set, n_steps, stream, &launched)) return rc;
-        if (launched) return SGX_OK;
-    }
-    for (int32_t i = 0; i < n_steps; ++i) {
-        p.io = ios[(first_set + i) % n_sets];
-        if (int rc = launch_step(h, p, stream, n_sets)) return rc;
-    }
-    return SGX_OK;
+    return play_steps(h, p, OutSets{ios, n_sets, false, 0, 0, 0}, first_set, n_steps, stream);
 }
 
 // sgx_step_n into a trajectory buffer: slot (first_slot + t) % n_slots of tensors with a leading slot axis receives step t's outputs.
@@ -1539,16 +1486,7 @@ SGX_API int sgx_step_traj(sgx_env *h, const sgx_traj_io *t, int32_t first_slot, 
                            : (io.flags & SGX_STEP_MASK_1D)      ? cells * (h->cfg.rows + h->cfg.cols) + 1 : cells * h->K;
     const OutSets slots{&t->io, t->n_slots, true, io.obs_dev ? t->slot_envs * obs_env : 0, io.fobs_dev ? t->slot_envs * cells * lut_channels(true, original) * 4 : 0,
                         io.mask_dev ? t->slot_envs * mask_env : 0};
-    {
-        bool launched = false;
-        if (int rc = launch_lane_steps(h, p, slots, first_slot, n_steps, stream, &launched)) return rc;
-        if (launched) return SGX_OK;
-        if (int rc = launch_wave_steps(h, p, slots, first_slot, n_steps, stream, &launched)) return rc;
-        if (launched) return SGX_OK;
-    }
-    for (int32_t i = 0; i < n_steps; ++i)
-        if (int rc = launch_set_step(h, p, slots, (int32_t)(((int64_t)first_slot + i) % t->n_slots), stream)) return rc;
-    return SGX_OK;
+    return play_steps(h, p, slots, first_slot, n_steps, stream);
 }
 
 SGX_API int sgx_rollout(sgx_env *h, const sgx_step_io *io, int32_t n_steps, int32_t chains, void *stream) {
@@ -1562,34 +1500,23 @@ SGX_API int sgx_rollout(sgx_env *h, const sgx_step_io *io, int32_t n_steps, int3
     // the chip part empty -- boards of up to 36 cells (Micro +19 %, Tiny +4 %, 5x5 +3 %, 6x6 +5 %) and boards whose cell count is no
     // multiple of 4 (15x15 +4 %) -- and lose 2-5 % on 8x8 / 10x10, whose single launch already streams at the memory rate
     SGX_ON_DEVICE(h->device);
+    KParams p = make_params(h);
+    p.mode = 0;
+    p.io = *io;
     if (chains == 0) {
-        // ... and since round 5 boards of at most 16 cells have something better than two chains of launches: all steps in ONE launch
-        // (lane_steps_kernel: Micro 29 us per step against 35 with two chains) wherever the call is eligible
-        KParams p0 = make_params(h);
-        p0.mode = 0;
+        // ... and since round 5 something better than chains of launches where the call is eligible: all steps in ONE launch -- boards of
+        // at most 16 cells lane_steps_kernel (Micro 29 us per step against 35 with two chains), the other boards steps_kernel, faster than
+        // two chains of launches on every board since its parameter reads are scalar loads (6x6: 97-99 against 101 us per step, 5x5: 71
+        // against 91; profiles/r05_variant_bench.log)
         bool launched = false;
-        const OutSets one{io, 1, false, 0, 0, 0};
-        if (int rc = launch_lane_steps(h, p0, one, 0, n_steps, stream, &launched)) return rc;
-        if (launched) return SGX_OK;
-        // ... and the other boards the multi-step launch of the wave-per-game kernels (steps_kernel): faster than two chains of launches on
-        // every board since its parameter reads are scalar loads (6x6: 97-99 against 101 us per step, 5x5: 71 against 91; profiles/r05_variant_bench.log)
-        if (int rc = launch_wave_steps(h, p0, one, 0, n_steps, stream, &launched)) return rc;
+        if (int rc = multi_steps(h, p, OutSets{io, 1, false, 0, 0, 0}, 0, n_steps, stream, &launched)) return rc;
         if (launched) return SGX_OK;
         chains = (cells <= 36 || cells % 4 != 0) ? 2 : 1;
     }
     const int64_t unit = 8 * 8 * (cells <= 16 ? 4 : (cells <= 32 ? 2 : 1));     // 8 workgroups x SGX_WPB waves x Geo::GPW games
     int64_t per = (h->n_envs / chains) / unit * unit;
     if (chains == 1 || per == 0 || n_steps == 0) return sgx_step_n(h, io, n_steps, stream);
-    if (!h->chain_fork) HIP_TRY(hipEventCreateWithFlags(&h->chain_fork, hipEventDisableTiming));
-    for (int c = 0; c < chains; ++c) {
-        if (!h->chain_stream[c]) HIP_TRY(hipStreamCreateWithFlags(&h->chain_stream[c], hipStreamNonBlocking));
-        if (!h->chain_join[c]) HIP_TRY(hipEventCreateWithFlags(&h->chain_join[c], hipEventDisableTiming));
-    }
-    KParams p = make_params(h);
-    p.mode = 0;
-    p.io = *io;
-    HIP_TRY(hipEventRecord(h->chain_fork, (hipStream_t)stream));
-    for (int c = 0; c < chains; ++c) HIP_TRY(hipStreamWaitEvent(h->chain_stream[c], h->chain_fork, 0));
+    if (int rc = fork_chains(h, chains, (hipStream_t)stream)) return rc;
     // Submission order: blocks of steps chain by chain.  (Alternating the stream with every launch costs more than the overlap
     // gains -- 65,536 Micro games: 107 us per step against 44 us with one chain; each switch of the submitting queue is a host
     // round trip.)
@@ -1616,16 +1543,13 @@ SGX_API int sgx_decode_obs(sgx_env *h, const uint8_t *compact_dev, float *obs_de
     if ((reinterpret_cast<uintptr_t>(obs_dev) & 15) && (h->cfg.rows * h->cfg.cols) % 4 == 0)
         return fail(SGX_EINVAL, "sgx_decode_obs: obs_dev must be 16-byte aligned%s");
     SGX_ON_DEVICE(h->device);
-    const int64_t obs_bytes = h->n_envs * (int64_t)h->cfg.rows * h->cfg.cols * OBS_CH * 4;
-    const int nt = h->nt_mode < 0 ? (obs_bytes > (int64_t)300 * 1000 * 1000 ? 1 : 0) : h->nt_mode;
-#define CALL_DECODE_OBS(R, C)                                                                                              \
-    do {                                                                                                                   \
-        using G_ = Geo<R, C>;                                                                                              \
-        const unsigned grid = (unsigned)((h->n_envs + G_::WPB * G_::GPW - 1) / (G_::WPB * G_::GPW));                       \
-        decode_obs_kernel<R, C><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(compact_dev, compact_obs_stride(h), compact_capacity(h), obs_dev, h->n_envs, nt); \
-    } while (0)
-    DISPATCH_GEOMETRY(h, CALL_DECODE_OBS);
-#undef CALL_DECODE_OBS
+    const int nt = nt_for(h, h->n_envs * (int64_t)h->cfg.rows * h->cfg.cols * OBS_CH * 4);
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            using G = Geo<R, C>;
+            const unsigned grid = (unsigned)((h->n_envs + G::WPB * G::GPW - 1) / (G::WPB * G::GPW));
+            decode_obs_kernel<R, C><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(compact_dev, compact_obs_stride(h), compact_capacity(h), obs_dev, h->n_envs, nt);
+        })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
@@ -1634,14 +1558,12 @@ SGX_API int sgx_decode_mask(sgx_env *h, const uint32_t *bits_dev, uint8_t *mask_
     if (!h || !bits_dev || !mask_dev) return fail(SGX_EINVAL, "NULL argument%s");
     if (reinterpret_cast<uintptr_t>(bits_dev) & 15) return fail(SGX_EINVAL, "sgx_decode_mask: bits_dev must be 16-byte aligned%s");
     SGX_ON_DEVICE(h->device);
-#define CALL_DECODE_MASK(R, C)                                                                                             \
-    do {                                                                                                                   \
-        using G_ = Geo<R, C>;                                                                                              \
-        const unsigned grid = (unsigned)((h->n_envs + G_::WPB * G_::GPW - 1) / (G_::WPB * G_::GPW));                       \
-        decode_mask_kernel<R, C><<<grid, 64 * G_::WPB, 0, (hipStream_t)stream>>>(bits_dev, mask_dev, h->n_envs);           \
-    } while (0)
-    DISPATCH_GEOMETRY(h, CALL_DECODE_MASK);
-#undef CALL_DECODE_MASK
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            using G = Geo<R, C>;
+            const unsigned grid = (unsigned)((h->n_envs + G::WPB * G::GPW - 1) / (G::WPB * G::GPW));
+            decode_mask_kernel<R, C><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(bits_dev, mask_dev, h->n_envs);
+        })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
@@ -1650,9 +1572,9 @@ SGX_API int sgx_sample_valid(sgx_env *h, const uint8_t *mask_dev, int32_t *actio
     if (!h || !mask_dev || !actions_dev) return fail(SGX_EINVAL, "NULL argument%s");
     SGX_ON_DEVICE(h->device);
     KParams p = make_params(h);
-#define CALL_SAMPLE(R, C) sample_kernel<R, C><<<(unsigned)h->n_envs, 64, 0, (hipStream_t)stream>>>(p, mask_dev, actions_dev)
-    DISPATCH_GEOMETRY(h, CALL_SAMPLE);
-#undef CALL_SAMPLE
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            sample_kernel<decltype(r)::value, decltype(c)::value><<<(unsigned)h->n_envs, 64, 0, (hipStream_t)stream>>>(p, mask_dev, actions_dev);
+        })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
@@ -1671,22 +1593,24 @@ SGX_API int sgx_choose_actions(sgx_env *h, const float *logits_dev, const void *
     const int64_t na = (int64_t)h->cfg.rows * h->cfg.cols * h->K;
     // rows of 4 actions per lane where every game's logits start on a 16-byte and its mask on a 4-byte boundary
     const bool vec4 = na % 4 == 0 && !(reinterpret_cast<uintptr_t>(logits_dev) & 15) && !(reinterpret_cast<uintptr_t>(mask_dev) & 3);
-#define CALL_CHOOSE_K(R, C, V, B)                                                                                                    \
-    do {                                                                                                                             \
-        using CG_ = ChooseGeo<Geo<R, C>, V>;                                                                                         \
-        choose_kernel<R, C, V, B><<<(unsigned)((h->n_envs + CG_::GAMES - 1) / CG_::GAMES), 64 * CG_::WAVES, 0, (hipStream_t)stream>>>( \
-            p, logits_dev, mask_dev, scale, actions_dev);                                                                    \
-    } while (0)
-#define CALL_CHOOSE(R, C)                                                                 \
-    do {                                                                                  \
-        if constexpr ((Geo<R, C>::NA % 4) == 0) {                                         \
-            if (vec4) { if (bits) CALL_CHOOSE_K(R, C, 4, true); else CALL_CHOOSE_K(R, C, 4, false); break; } \
-        }                                                                                 \
-        if (bits) CALL_CHOOSE_K(R, C, 1, true); else CALL_CHOOSE_K(R, C, 1, false);       \
-    } while (0)
-    DISPATCH_GEOMETRY(h, CALL_CHOOSE);
-#undef CALL_CHOOSE
-#undef CALL_CHOOSE_K
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            auto launch = [&](auto vec, auto bits_c) {
+                constexpr int V = decltype(vec)::value;
+                constexpr bool B = decltype(bits_c)::value;
+                using CG = ChooseGeo<Geo<R, C>, V>;
+                choose_kernel<R, C, V, B><<<(unsigned)((h->n_envs + CG::GAMES - 1) / CG::GAMES), 64 * CG::WAVES, 0, (hipStream_t)stream>>>(
+                    p, logits_dev, mask_dev, scale, actions_dev);
+            };
+            auto with_bits = [&](auto vec) {
+                if (bits) launch(vec, bool_c<true>());
+                else launch(vec, bool_c<false>());
+            };
+            if constexpr (Geo<R, C>::NA % 4 == 0) {
+                if (vec4) return with_bits(int_c<4>());
+            }
+            with_bits(int_c<1>());
+        })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
@@ -1702,26 +1626,25 @@ unsigned state_grid(const sgx_env *h, KParams &p) {
     p.map_mode = h->map_mode; p.map_arg = h->map_arg;
     return shares_for(p, p.n_envs - p.env_first, w);
 }
-bool states_stream_past_cache(const sgx_env *h) {
-    return h->n_envs * (int64_t)SGX_STATE_LAYERS * h->cfg.rows * h->cfg.cols * 8 > (int64_t)300 * 1000 * 1000;
-}
+// bytes of the batch's int64 states
+int64_t state_bytes(const sgx_env *h) { return h->n_envs * (int64_t)SGX_STATE_LAYERS * h->cfg.rows * h->cfg.cols * 8; }
 int launch_export(sgx_env *h, const KParams &p_in, int64_t *state_dev, int8_t *player_dev, hipStream_t stream) {
     // (the int64 layout is 27 KB per 10x10 state: past the Infinity Cache the layers leave as non-temporal stores, like the observations)
-    const int nt = h->nt_mode < 0 ? states_stream_past_cache(h) : h->nt_mode;
+    const int nt = nt_for(h, state_bytes(h));
     KParams p = p_in;
     const unsigned grid = state_grid(h, p);
-#define CALL_EXPORT(R, C) export_kernel<R, C><<<grid, 256, 0, stream>>>(p, state_dev, player_dev, nt)
-    DISPATCH_GEOMETRY(h, CALL_EXPORT);
-#undef CALL_EXPORT
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            export_kernel<decltype(r)::value, decltype(c)::value><<<grid, 256, 0, stream>>>(p, state_dev, player_dev, nt);
+        })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
 int launch_import(sgx_env *h, const KParams &p_in, const int64_t *state_dev, const int8_t *player_dev, uint8_t *sanitised_dev, hipStream_t stream) {
     KParams p = p_in;
     const unsigned grid = state_grid(h, p);
-#define CALL_IMPORT(R, C) import_kernel<R, C><<<grid, 256, 0, stream>>>(p, state_dev, player_dev, sanitised_dev)
-    DISPATCH_GEOMETRY(h, CALL_IMPORT);
-#undef CALL_IMPORT
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            import_kernel<decltype(r)::value, decltype(c)::value><<<grid, 256, 0, stream>>>(p, state_dev, player_dev, sanitised_dev);
+        })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
@@ -1751,6 +1674,14 @@ int redo_list_reset(sgx_env *h, KParams &p, hipStream_t stream) {
 }
 // the general-state pass: a small persistent grid that walks the list
 unsigned redo_grid(const sgx_env *h) { return (unsigned)(h->n_envs < 2048 ? h->n_envs : 2048); }
+// f(bool_c<MAPPED>, bool_c<OBS>): the states_kernel instantiation of sgx_step_states' outputs (state-coordinate masks, an observation)
+template <class F>
+void with_states_io(bool mapped, bool obs, F &&f) {
+    if (mapped && obs) f(bool_c<true>(), bool_c<true>());
+    else if (mapped) f(bool_c<true>(), bool_c<false>());
+    else if (obs) f(bool_c<false>(), bool_c<true>());
+    else f(bool_c<false>(), bool_c<false>());
+}
 }  // namespace
 
 // get_next_state (penv:148-155) and friends on caller-provided int64 states in ONE call: import -> step -> export, the batch split
@@ -1761,15 +1692,19 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
     if (io->auto_reset || io->next_actions_dev) return fail(SGX_EINVAL, "sgx_step_states: no auto_reset, no sampled next actions%s");
     if (io->flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) return fail(SGX_EINVAL, "sgx_step_states: no compact outputs%s");
     if (chains < 1 || chains > SGX_MAX_CHAINS) return fail(SGX_EINVAL, "chains out of range%s");
-    // Will a general-state pass run behind this call?  (The fused one-launch path always has one; the three-launch paths have one except for
-    // state-coordinate masks together with another observation kind: the same conditions as `general` / `general_small` below.)
-    const bool will_redo = [&] {
-        const int cells = h->cfg.rows * h->cfg.cols;
-        const bool k0 = !io->fobs_dev && !io->final_fobs_dev && !(io->flags & SGX_STEP_ORIGINAL_CHANNELS);
-        const bool mapped = (io->flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) != 0;
-        return h->general_states != 0 && cells <= 256 && (k0 || !mapped);
-    }();
-    if (will_redo) {
+    const int cells = h->cfg.rows * h->cfg.cols;
+    const bool kind0 = !io->fobs_dev && !io->final_fobs_dev && !(io->flags & SGX_STEP_ORIGINAL_CHANNELS);
+    const bool mapped = (io->flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) != 0;
+    const bool obs = io->obs_dev || io->final_obs_dev;
+    // one-game-per-wave boards, partial-observation kinds: ONE fused launch, the record never leaves LDS between the three steps
+    const bool fused = kind0 && cells > 32 && cells <= 256;
+    // Second pass (sgx_set_general_states, on by default): the states the first pass had to alter -- more than two recent-move cells per
+    // player, more capture cells than pieces, more than 8 captures on a cell: things play cannot produce but penv's pure functions
+    // accept -- are redone from the caller's int64 input on the general-state variant of the geometry (Geo<R, C, 1>); every other
+    // block of that launch leaves at once.  Not: boards of more than 256 cells; state-coordinate masks together with another observation
+    // kind (which the fused path does not take).
+    const bool general = h->general_states != 0 && cells <= 256 && (kind0 || !mapped);
+    if (general) {
         // The general-state pass re-reads the caller's INPUT after the first pass has written the outputs: a state stepped in place would
         // be redone from its own successor (stepped twice, or judged invalid) without anybody noticing.  (Calls behind which no such pass
         // runs may step a batch in place: every state is read completely before its successor is written.)
@@ -1777,8 +1712,7 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
             const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
             return a && b && a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
         };
-        const int64_t state_bytes = h->n_envs * (int64_t)SGX_STATE_LAYERS * h->cfg.rows * h->cfg.cols * 8;
-        if (overlap(state_in_dev, state_bytes, state_out_dev, state_bytes) || overlap(player_in_dev, h->n_envs, player_out_dev, h->n_envs))
+        if (overlap(state_in_dev, state_bytes(h), state_out_dev, state_bytes(h)) || overlap(player_in_dev, h->n_envs, player_out_dev, h->n_envs))
             return fail(SGX_EINVAL, "sgx_step_states: state_out_dev / player_out_dev overlap the inputs, which the general-state pass reads again "
                                     "after the outputs are written; pass distinct buffers or switch the pass off (sgx_set_general_states(h, 0))%s");
     }
@@ -1789,128 +1723,96 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
     KParams p = make_params(h);
     p.mode = io->actions_dev ? 0 : 1;        // no actions: observe -- masks / observations of the given states, nothing is played
     p.io = *io;
-    const bool kind0 = !io->fobs_dev && !io->final_fobs_dev && !(io->flags & SGX_STEP_ORIGINAL_CHANNELS);
-    if (kind0 && h->cfg.rows * h->cfg.cols > 32 && h->cfg.rows * h->cfg.cols <= 256) {
-        // one-game-per-wave boards, partial-observation kinds: ONE fused launch, the record never leaves LDS between the three steps
-        if (int rc = check_step_io(h, p)) return rc;
-        const int nt = h->nt_mode < 0 ? states_stream_past_cache(h) : h->nt_mode;
-        const unsigned grid = state_grid(h, p);
-        p.nt_stores = h->nt_mode < 0 ? (launch_streams_past_cache(h, p) ? 1 : 0) : h->nt_mode;
-        const bool mapped = (io->flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) != 0;
-        const bool obs = io->obs_dev || io->final_obs_dev;
-        // Second pass (sgx_set_general_states, on by default): the states the first pass had to alter -- more than two recent-move cells per
-        // player, more capture cells than pieces, more than 8 captures on a cell: things play cannot produce but penv's pure functions
-        // accept -- are redone from the caller's int64 input on the general-state variant of the geometry (Geo<R, C, 1>); every other
-        // block of that launch leaves at once.  It needs the flags even when the caller did not ask for them.
-        const bool general = h->general_states != 0;
-        uint8_t *flags_dev = sanitised_dev;
-        if (general && !flags_dev) {
-            if (!h->san_flags) HIP_TRY(hipMalloc((void **)&h->san_flags, (size_t)h->n_envs));
-            flags_dev = h->san_flags;
-        }
-        if (general)
-            if (int rc = redo_list_reset(h, p, (hipStream_t)stream)) return rc;
+    if (int rc = check_step_io(h, p)) return rc;
+    // the general-state pass needs the flags even when the caller did not ask for them
+    uint8_t *flags_dev = sanitised_dev;
+    if (general && !flags_dev) {
+        if (!h->san_flags) HIP_TRY(hipMalloc((void **)&h->san_flags, (size_t)h->n_envs));
+        flags_dev = h->san_flags;
+    }
+    if (general)
+        if (int rc = redo_list_reset(h, p, (hipStream_t)stream)) return rc;       // (before the chains fork: their imports append to the list)
+    int32_t *const redo_count = h->redo_list ? h->redo_list + h->n_envs : nullptr;
+    const int nt = nt_for(h, state_bytes(h));
+    const hipStream_t st = (hipStream_t)stream;
+    if (fused) {
+        const unsigned grid = state_grid(h, p), grid_big = redo_grid(h);
+        p.nt_stores = nt_for(h, launch_obs_bytes(h, p));
         KParams pbig = p;                                   // the general-state pass appends nothing
         pbig.flag_list = pbig.flag_count = nullptr;
-        const unsigned grid_big = redo_grid(h);
-#define CALL_STATES_K(R, C, M, O, V) states_kernel<R, C, M, O, V><<<(V) ? grid_big : grid, states_threads<M, O>(), 0, (hipStream_t)stream>>>((V) ? pbig : p, state_in_dev, player_in_dev, flags_dev, state_out_dev, player_out_dev, nt, h->redo_list, h->redo_list ? h->redo_list + h->n_envs : nullptr)
-#define CALL_STATES_V(R, C, V)                                                                                              \
-    do {                                                                                                                    \
-        if constexpr (Geo<R, C>::LPG == 64 && !Geo<R, C>::WIDE) {                                                           \
-            if (mapped && obs) CALL_STATES_K(R, C, true, true, V);                                                          \
-            else if (mapped) CALL_STATES_K(R, C, true, false, V);                                                           \
-            else if (obs) CALL_STATES_K(R, C, false, true, V);                                                              \
-            else CALL_STATES_K(R, C, false, false, V);                                                                      \
-        }                                                                                                                   \
-    } while (0)
-#define CALL_STATES(R, C) CALL_STATES_V(R, C, 0)
-#define CALL_STATES_BIG(R, C) CALL_STATES_V(R, C, 1)
-        DISPATCH_GEOMETRY(h, CALL_STATES);
+        auto pass = [&](auto var) {
+            constexpr int VAR = decltype(var)::value;
+            return for_geometry(h, [&](auto r, auto c) {
+                constexpr int R = decltype(r)::value, C = decltype(c)::value;
+                if constexpr (Geo<R, C>::LPG == 64 && !Geo<R, C>::WIDE)
+                    with_states_io(mapped, obs, [&](auto m, auto o) {
+                        constexpr bool M = decltype(m)::value, O = decltype(o)::value;
+                        states_kernel<R, C, M, O, VAR><<<VAR ? grid_big : grid, states_threads<M, O>(), 0, st>>>(
+                            VAR ? pbig : p, state_in_dev, player_in_dev, flags_dev, state_out_dev, player_out_dev, nt, h->redo_list, redo_count);
+                    });
+            });
+        };
+        if (int rc = pass(int_c<0>())) return rc;
         HIP_TRY(hipGetLastError());
         if (general) {
-            DISPATCH_GEOMETRY(h, CALL_STATES_BIG);
+            if (int rc = pass(int_c<1>())) return rc;
             HIP_TRY(hipGetLastError());
         }
-#undef CALL_STATES
-#undef CALL_STATES_BIG
-#undef CALL_STATES_V
-#undef CALL_STATES_K
         return SGX_OK;
     }
     // What the fused path above does not cover takes the three-launch path on packed records -- boards of up to 32 cells (several games per
     // wave) and the other observation kinds (79-channel, 'original' channels).  States the packed records cannot carry are then redone,
     // like above, by the general-state variant of the fused kernel, which is one game per wave on every board and takes the observation
-    // kind as a parameter.  (Not: boards of more than 256 cells; state-coordinate masks together with another observation kind.)
-    const int cells_ = h->cfg.rows * h->cfg.cols;
-    const bool mapped_ = (io->flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) != 0;
-    const bool general_small = h->general_states != 0 && cells_ <= 256 && (kind0 ? cells_ <= 32 : !mapped_);
-    uint8_t *flags_small = sanitised_dev;
-    if (general_small && !flags_small) {
-        if (!h->san_flags) HIP_TRY(hipMalloc((void **)&h->san_flags, (size_t)h->n_envs));
-        flags_small = h->san_flags;
-    }
-    if (general_small)
-        if (int rc = redo_list_reset(h, p, (hipStream_t)stream)) return rc;       // (before the chains fork: their imports append to the list)
-    auto second_pass_small = [&]() -> int {
-        if (!general_small) return SGX_OK;
-        if (int rc = check_step_io(h, p)) return rc;
+    // kind as a parameter.
+    auto second_pass = [&]() -> int {
+        if (!general) return SGX_OK;
         KParams q = p;
         q.env_first = 0;
         q.n_envs = h->n_envs;
         q.flag_list = q.flag_count = nullptr;
-        const int nt = h->nt_mode < 0 ? states_stream_past_cache(h) : h->nt_mode;
         const unsigned grid = redo_grid(h);
-        q.nt_stores = h->nt_mode < 0 ? (launch_streams_past_cache(h, q) ? 1 : 0) : h->nt_mode;
-        const bool obs = io->obs_dev || io->final_obs_dev;
+        q.nt_stores = nt_for(h, launch_obs_bytes(h, q));
         const int kindx = ((io->fobs_dev || io->final_fobs_dev) ? 1 : 0) | ((io->flags & SGX_STEP_ORIGINAL_CHANNELS) ? 2 : 0);
-#define CALL_STATES_SMALL_K(R, C, M, O) states_kernel<R, C, M, O, 1><<<grid, states_threads<M, O>(), 0, (hipStream_t)stream>>>(q, state_in_dev, player_in_dev, flags_small, state_out_dev, player_out_dev, nt, h->redo_list, h->redo_list + h->n_envs)
-#define CALL_STATES_KIND_K(R, C, KX) states_kernel<R, C, false, true, 1, KX><<<grid, states_threads<false, true>(), 0, (hipStream_t)stream>>>(q, state_in_dev, player_in_dev, flags_small, state_out_dev, player_out_dev, nt, h->redo_list, h->redo_list + h->n_envs)
-#define CALL_STATES_SMALL(R, C)                                                                                             \
-    do {                                                                                                                    \
-        if constexpr (!Geo<R, C>::WIDE) {                                                                                   \
-            if (kindx == 1) CALL_STATES_KIND_K(R, C, 1);                                                                    \
-            else if (kindx == 2) CALL_STATES_KIND_K(R, C, 2);                                                               \
-            else if (kindx == 3) CALL_STATES_KIND_K(R, C, 3);                                                               \
-            else if constexpr (Geo<R, C>::LPG != 64) {                                                                      \
-                if (mapped_ && obs) CALL_STATES_SMALL_K(R, C, true, true);                                                  \
-                else if (mapped_) CALL_STATES_SMALL_K(R, C, true, false);                                                   \
-                else if (obs) CALL_STATES_SMALL_K(R, C, false, true);                                                       \
-                else CALL_STATES_SMALL_K(R, C, false, false);                                                               \
-            }                                                                                                               \
-        }                                                                                                                   \
-    } while (0)
-        DISPATCH_GEOMETRY(h, CALL_STATES_SMALL);
-#undef CALL_STATES_SMALL
-#undef CALL_STATES_SMALL_K
-#undef CALL_STATES_KIND_K
+        if (int rc = for_geometry(h, [&](auto r, auto c) {
+                constexpr int R = decltype(r)::value, C = decltype(c)::value;
+                if constexpr (!Geo<R, C>::WIDE) {
+                    auto kind_pass = [&](auto kx) {
+                        states_kernel<R, C, false, true, 1, decltype(kx)::value><<<grid, states_threads<false, true>(), 0, st>>>(
+                            q, state_in_dev, player_in_dev, flags_dev, state_out_dev, player_out_dev, nt, h->redo_list, redo_count);
+                    };
+                    if (kindx == 1) kind_pass(int_c<1>());
+                    else if (kindx == 2) kind_pass(int_c<2>());
+                    else if (kindx == 3) kind_pass(int_c<3>());
+                    else if constexpr (Geo<R, C>::LPG != 64)
+                        with_states_io(mapped, obs, [&](auto m, auto o) {
+                            constexpr bool M = decltype(m)::value, O = decltype(o)::value;
+                            states_kernel<R, C, M, O, 1><<<grid, states_threads<M, O>(), 0, st>>>(
+                                q, state_in_dev, player_in_dev, flags_dev, state_out_dev, player_out_dev, nt, h->redo_list, redo_count);
+                        });
+                }
+            })) return rc;
         HIP_TRY(hipGetLastError());
         return SGX_OK;
     };
     if (chains == 1) {
-        if (int rc = launch_import(h, p, state_in_dev, player_in_dev, flags_small, (hipStream_t)stream)) return rc;
+        if (int rc = launch_import(h, p, state_in_dev, player_in_dev, flags_dev, st)) return rc;
         if (int rc = launch_step(h, p, stream)) return rc;
         if (state_out_dev)
-            if (int rc = launch_export(h, p, state_out_dev, player_out_dev, (hipStream_t)stream)) return rc;
-        return second_pass_small();
+            if (int rc = launch_export(h, p, state_out_dev, player_out_dev, st)) return rc;
+        return second_pass();
     }
-    if (!h->chain_fork) HIP_TRY(hipEventCreateWithFlags(&h->chain_fork, hipEventDisableTiming));
-    for (int c = 0; c < chains; ++c) {
-        if (!h->chain_stream[c]) HIP_TRY(hipStreamCreateWithFlags(&h->chain_stream[c], hipStreamNonBlocking));
-        if (!h->chain_join[c]) HIP_TRY(hipEventCreateWithFlags(&h->chain_join[c], hipEventDisableTiming));
-    }
-    HIP_TRY(hipEventRecord(h->chain_fork, (hipStream_t)stream));
-    for (int c = 0; c < chains; ++c) HIP_TRY(hipStreamWaitEvent(h->chain_stream[c], h->chain_fork, 0));
+    if (int rc = fork_chains(h, chains, st)) return rc;
     int rc = SGX_OK;
     for (int c = 0; c < chains && rc == SGX_OK; ++c) {
         KParams pc = p;
         pc.env_first = c * per;
         pc.n_envs = c == chains - 1 ? h->n_envs : (c + 1) * per;
-        rc = launch_import(h, pc, state_in_dev, player_in_dev, flags_small, h->chain_stream[c]);
+        rc = launch_import(h, pc, state_in_dev, player_in_dev, flags_dev, h->chain_stream[c]);
         if (rc == SGX_OK) rc = launch_step(h, pc, (void *)h->chain_stream[c]);
         if (rc == SGX_OK && state_out_dev) rc = launch_export(h, pc, state_out_dev, player_out_dev, h->chain_stream[c]);
     }
-    rc = join_chains(h, chains, (hipStream_t)stream, rc);     // (also after a failed launch: see sgx_rollout)
-    return rc != SGX_OK ? rc : second_pass_small();
+    rc = join_chains(h, chains, st, rc);     // (also after a failed launch: see sgx_rollout)
+    return rc != SGX_OK ? rc : second_pass();
 }
 
 SGX_API int sgx_import_state(sgx_env *h, const int64_t *state_dev, const int8_t *player_dev, void *stream) {

@@ -107,20 +107,26 @@ def test_every_entry_point_restores_the_callers_device():
     guard = src[src.index('struct DeviceGuard {'):src.index('#define SGX_ON_DEVICE')]
     rest = src.replace(guard, '')
     assert guard.count('hipSetDevice(') == 2 and 'hipSetDevice(' not in rest
-    parts = re.split(r'\nSGX_API ', src)[1:]
-    checked = 0
+    parts = [part + '\n' for part in re.split(r'\nSGX_API ', src)[1:]]
+    # the file's own helpers that launch or call HIP for the entry point that calls them
+    helpers = r'launch_(step|set_step|import|export)|step_single|play_steps|multi_steps|for_geometry|fork_chains|join_chains|pick_buffer'
+    checked = set()
     for part in parts:
         head = part[:part.index('(')]
         name = head.split()[-1].lstrip('*')
-        body = part[:part.index('\n}\n') + 3] if '\n}\n' in part else part
-        if '{' not in body.split('\n', 1)[0] or body.split('\n', 1)[0].rstrip().endswith('}'):
+        signature_end = part.index(')')                     # (no parameter list here holds a parenthesis; it may span several lines)
+        first_line = part[:part.index('\n', signature_end)]
+        if first_line.rstrip().endswith('}'):
             continue                                        # one-line getters touch no device
-        touches = re.search(r'\bhip[A-Z]\w*\(|<<<|\blaunch_(step|import|export)\(|\bstep_single\(', body)
+        assert first_line.rstrip().endswith('{'), name
+        body = part[:part.index('\n}\n') + 3]
+        touches = re.search(r'\bhip[A-Z]\w*\(|<<<|\bEventPair\b|\b(' + helpers + r')\(', body)
         if not touches:
             continue
         if name == 'sgx_destroy':
             assert 'DeviceGuard device_guard_(h->device);' in body
         else:
             assert 'SGX_ON_DEVICE(' in body, name
-        checked += 1
-    assert checked >= 20
+        checked.add(name)
+    assert {'sgx_step_traj', 'sgx_store_probe', 'sgx_step_states'} <= checked
+    assert len(checked) >= 28

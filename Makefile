@@ -13,8 +13,8 @@ test-gpu:         ## bit-exact GPU parity (MI355X)
 smoke:
 	$(PY) -c "import __graft_entry__ as g; g.build(); g.smoke()"
 
-bench:            ## one JSON line: env steps/s, roofline, cpu_baseline
-	$(PY) bench.py
+bench:            ## one JSON line: env steps/s, roofline, cpu_baseline, every leg
+	$(PY) bench.py --full
 
 pin-oracle:       ## build container only: diff the oracle against the imported reference, regenerate nothing
 	$(PY) -m tools.oracle.check_oracle_vs_reference --games 36

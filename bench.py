@@ -1,25 +1,30 @@
 """bench.py -- env steps/sec of the batched env.step() hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run measures the headline alone: set-up (GPU wake-up, the env, the output placement search and the ring of output sets), W
+warm-up steps, the K timed steps, --dump-outputs if asked, the line.  `--full` adds everything else the line can carry: the oracle check
+of the timed envs and the outputs checksum, the solo anchors and scaling legs of a multi-GPU line, and on one GPU the legs after the
+headline, the store probe, the live counter passes and the CPU baseline; the --no-* options drop single legs of a --full run.
 
 Workload.  BASELINE.json configs[1] on EVERY GPU: 65,536 concurrent Barrage games per GPU, synthetic
 random-valid-action rollout with auto-reset, setups from the Gravon table, everything keyed by the counter RNG on (seed, global env id,
 game, turn) -- so `value` over --gpus 1 / 2 / 4 / 8 is the weak-scaling curve of ONE workload ("scaling": "weak": per-GPU work fixed).
-Every multi-GPU line is self-anchoring: before the ranks run a workload side by side, rank 0 times the same per-GPU workload ALONE (the
-other ranks parked at a host-side barrier; same process, env object and buffers), and the line reports config.solo, config.scaling_x =
-value / solo value and config.per_gpu_value_min_over_solo.  BASELINE configs[4] (262,144 games per GPU, 2,097,152 on
-8 GPUs) is config.scaling_legs[0] of every multi-GPU line (with its own solo anchor and scaling_x; the strong split of 2,097,152 games
-follows where it is a different size) and config.other_workloads[3] of the 1-GPU line; --envs / --total-envs override.
+Every --full multi-GPU line is self-anchoring: before the ranks run a workload side by side, rank 0 times the same per-GPU workload ALONE
+(the other ranks parked at a host-side barrier; same process, env object and buffers), and the line reports config.solo, config.scaling_x
+= value / solo value and config.per_gpu_value_min_over_solo.  BASELINE configs[4] (262,144 games per GPU, 2,097,152
+on 8 GPUs) is config.scaling_legs[0] of every --full multi-GPU line (with its own solo anchor and scaling_x; the strong split of 2,097,152
+games follows where it is a different size) and config.other_workloads[3] of the --full 1-GPU line; --envs / --total-envs override.
 One "step" = one batched env.step() over all of the rank's games: action in, move/combat/capture applied, win/draw detection,
 next mover's valid-actions mask (uint8 [R,C,K]) and normalised partial observation (float32 [R,C,67]) written to HBM, plus the
 next random valid action.  Inputs are resident in HBM when the timed region starts.  On one GPU the K timed steps write their outputs
 round-robin into THREE output sets (sgx_step_ring: a trajectory buffer of the last three steps): what a learner that stores every step
 does, and the rate a policy that reads the outputs between steps sees (config.consumer_in_loop) -- nothing a launch writes can still be
-cached when its addresses are written again, so `value` and `roofline` are DRAM-side figures.  The in-place variant (one set of
-tensors rewritten every step: the headline of rounds 1-3, 8-10 % faster because rewriting the same 1-2 GB back to back is) follows as
-config.in_place; config.no_settle is the headline's K steps once more without the untimed gpu_settle launches.  --output-sets 1 makes
-in place the headline again.
+cached when its addresses are written again, so `value` and `roofline` are DRAM-side figures.  With --full the in-place variant (one
+set of tensors rewritten every step: the headline of rounds 1-3, 8-10 % faster because rewriting the same 1-2 GB back to back is) follows
+as config.in_place, and config.no_settle is the headline's K steps once more without the untimed gpu_settle launches.  --output-sets 1
+makes in place the headline again.
 
 Multi-GPU: one process per GPU.  Under a launcher (RANK / WORLD_SIZE set) this process is one rank; run directly with
 --gpus N > 1 it starts the N ranks itself as fresh child processes BEFORE anything touches the GPU (a process that has
@@ -39,8 +44,9 @@ Prints ONE JSON line (rank 0) with
                   build id matches); `frac_untuned` = B_min over the observe launch of the process's plain first allocation;
                   `survey_8d` = SURVEY 8d's 33,848 B per step x games / launch time, a labelled comparison only (the kernel moves
                   fewer bytes than that formula assumes, so it is not a fraction of anything);
+and, with --full (the fields stay in a plain line, null or 0):
   `verified_envs` sampled envs of the very env object that was timed, checked after the timed region against the CPU oracle
-                  replaying the same number of steps (outputs of the last step, turn and game counters);
+                  replaying the same number of steps (outputs of the last step, turn and game counters; also --verify-envs N);
   `config.in_place`   the in-place leg (+ `config.two_chains`); `config.consumer_in_loop`  sgx_step alternating with a device policy that READS
                   the observation and the mask (examples/batched_policy_loop.py), non-temporal against plain stores under that reader;
   `config.other_workloads`  BASELINE configs 3 and 4 and the reference's default BOTH_OBSERVATIONS mode (1-GPU run only);
@@ -255,15 +261,19 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=64)
     ap.add_argument('--envs', type=int, default=None,
                     help='games per GPU (weak scaling: fixed as --gpus grows); default 65,536 (BASELINE config 2) on ANY number of GPUs, so '
-                         'that `value` over --gpus 1 / 2 / 4 / 8 is a curve of one workload; config 5 (262,144 per GPU) is a leg of every line')
+                         'that `value` over --gpus 1 / 2 / 4 / 8 is a curve of one workload; config 5 (262,144 per GPU) is a leg of every --full line')
     ap.add_argument('--total-envs', type=int, default=0,
                     help='strong scaling instead (SURVEY 8d config 5): this many games in total, split over the ranks')
+    ap.add_argument('--full', action='store_true',
+                    help="also run everything the headline does not need: the oracle check of the timed envs and the outputs checksum, the "
+                         "solo anchors and scaling legs of a multi-GPU line, and on one GPU the legs after the headline, the store probe, the "
+                         "live counter passes and the CPU baseline (a plain run: set-up, warm-up, the timed steps, --dump-outputs, the line)")
     ap.add_argument('--strong-total', type=int, default=None,
-                    help='games of the strong-scaling LEG reported next to the weak headline (default 2,097,152 when --gpus > 1, '
+                    help='games of the strong-scaling LEG reported next to the weak headline (default with --full: 2,097,152 when --gpus > 1; '
                          '0 = skip; pass it explicitly to get the leg on one GPU)')
     ap.add_argument('--leg-envs', type=int, default=None,
-                    help="games per GPU of the multi-GPU line's first scaling leg (default 262,144 = BASELINE config 5 when --envs is "
-                         "defaulted, else no leg; 0 = skip)")
+                    help="games per GPU of the multi-GPU line's first scaling leg (default with --full: 262,144 = BASELINE config 5 when --envs "
+                         "is defaulted, else no leg; 0 = skip)")
     ap.add_argument('--version', default='barrage')
     ap.add_argument('--unfused', action='store_true', help='sample actions with the standalone sampler kernel')
     ap.add_argument('--full-obs', action='store_true',
@@ -303,16 +313,16 @@ def parse_args(argv=None):
                          '(1 = sgx_step_n, one launch per step: what the headline uses, so that the per-launch figures are per step)')
     ap.add_argument('--no-two-chains', action='store_true', help='skip the two-concurrent-chains leg after the headline (profiling runs: '
                     'keeps the kernel statistics to one launch shape)')
-    ap.add_argument('--verify-envs', type=int, default=32,
-                    help='envs per rank checked against the CPU oracle after the timed region (0 = off)')
+    ap.add_argument('--verify-envs', type=int, default=None,
+                    help='envs per rank checked against the CPU oracle after the timed region (default: 32 with --full, else 0 = off)')
     ap.add_argument('--devices', default=None,
                     help='comma-separated device index per local rank (default: LOCAL_RANK); "0,0" runs two ranks on one GPU '
                          '(tests/test_gpu_two_ranks.py)')
     ap.add_argument('--backend', default=None, choices=('nccl', 'gloo'),
                     help='process-group backend of the reporting reductions (default nccl = RCCL; gloo when ranks share a GPU)')
     ap.add_argument('--no-live-traffic', action='store_true',
-                    help="roofline.traffic from profiles/traffic.json only (static); default on one GPU: measured now by two short children of this "
-                         "run under rocprofv3 --pmc (about 20 s), the static entry kept as roofline.traffic_static")
+                    help="roofline.traffic from profiles/traffic.json only (static); default of --full on one GPU: measured now by two short "
+                         "children of this run under rocprofv3 --pmc (about 20 s), the static entry kept as roofline.traffic_static")
     ap.add_argument('--no-store-probe', action='store_true',
                     help='skip roofline.store_probe (the store-only kernel on the headline ring buffers: three payloads per set and one long launch)')
     ap.add_argument('--no-trajectory-leg', action='store_true', help='skip config.trajectory (the rollout into a 64-slot trajectory buffer, sgx_step_traj)')
@@ -333,8 +343,8 @@ def parse_args(argv=None):
         ap.error("--dump-outputs needs a real run (the --dry-run stub computes nothing)")
     if args.envs is None:
         # the SAME per-GPU workload on any number of GPUs (BASELINE config 2 on every GPU): `value` over --gpus 1 / 2 / 4 / 8 is a weak-scaling
-        # curve of one workload.  BASELINE config 5 (262,144 games per GPU, 2,097,152 on 8) is config.scaling_legs[0] of every multi-GPU
-        # line and config.other_workloads[3] of the 1-GPU line, each with its own anchor.
+        # curve of one workload.  BASELINE config 5 (262,144 games per GPU, 2,097,152 on 8) is config.scaling_legs[0] of every --full
+        # multi-GPU line and config.other_workloads[3] of the --full 1-GPU line, each with its own anchor.
         args.envs = GAMES_1GPU
         args.envs_defaulted = True
     else:
@@ -344,10 +354,13 @@ def parse_args(argv=None):
     if args.output_sets < 1:
         ap.error("--output-sets must be >= 1")
     args.rotate_sets = 3           # the ring of the Micro leg (other_workloads)
+    if args.verify_envs is None:
+        args.verify_envs = 32 if args.full else 0
+    full_multi = args.full and args.gpus > 1 and not args.total_envs and args.envs_defaulted
     if args.leg_envs is None:
-        args.leg_envs = GAMES_PER_GPU_MULTI if (args.gpus > 1 and not args.total_envs and args.envs_defaulted) else 0
+        args.leg_envs = GAMES_PER_GPU_MULTI if full_multi else 0
     if args.strong_total is None:
-        args.strong_total = STRONG_TOTAL if (args.gpus > 1 and not args.total_envs and args.envs_defaulted) else 0
+        args.strong_total = STRONG_TOTAL if full_multi else 0
     return args
 
 
@@ -357,14 +370,14 @@ from bench_launcher import Rank, launch_ranks, visible_gpus  # noqa: E402,F401  
 
 def legs_for(rank, world, args, dry=False):
     """Which of the line's optional legs THIS rank runs (a pure function of its arguments: tests/test_bench_launcher_cpu.py checks every
-    rank of an 8-rank job).  The CPU baseline, the live counter passes (children of rank 0 under rocprofv3), the store probe, the facade
-    and the other workloads belong to rank 0 of a ONE-GPU run only; a multi-GPU line spends its time on the scaling legs, which every
-    rank takes part in."""
+    rank of an 8-rank job).  A plain run has none but a scaling leg its arguments name by size; the rest comes with --full.  The CPU
+    baseline, the live counter passes (children of rank 0 under rocprofv3), the store probe, the facade and the other workloads belong to
+    rank 0 of a ONE-GPU run only; a multi-GPU line spends its time on the scaling legs, which every rank takes part in."""
     legs = set()
     # (the scaling legs: every rank takes part, same barriers)
     if not args.no_scaling_legs and ((world > 1 and not args.total_envs and args.leg_envs) or args.strong_total):
         legs.add('scaling_legs')
-    if dry:
+    if dry or not args.full:
         return legs
     if SETTLE_SECONDS > 0 and not args.no_settle_leg:
         legs.update(('no_settle', 'one_launch_per_step'))
@@ -941,17 +954,18 @@ def run_rank(args):      # noqa: C901
                                                      "used": reps[0]['used']}
             if reps[0]['used']:
                 placement["kept_us"] = round(min(reps[0]['obs']), 1)
-    # several GPUs: rank 0 times this per-GPU workload ALONE first (the others parked, no GPU work), so that the line carries its own anchor
-    solo = solo_anchor(rk, env, args.steps, args.warmup, unfused=args.unfused, chains=args.chains, ring=headline_ring)
+    # several GPUs, --full: rank 0 times this per-GPU workload ALONE first (the others parked, no GPU work), so that the line carries its own anchor
+    solo = solo_anchor(rk, env, args.steps, args.warmup, unfused=args.unfused, chains=args.chains, ring=headline_ring) if args.full else None
     elapsed, dev_ms, own, games, invalid = time_workload(rk, env, args.steps, args.warmup, args.unfused, args.chains, ring=headline_ring)
     assert invalid == 0, "rollout produced invalid actions"
     fused = fused_steps_of(env, args.steps) if not dry else 1           # multi-step launches: the record travels once per launch, not per step
-    # outside the timed region: the envs that were just timed against the CPU oracle, and the sharding-independent checksum
+    # outside the timed region, --full (or --verify-envs N for the first): the envs that were just timed against the CPU oracle, and the
+    # sharding-independent checksum
     checked = verify_against_oracle(env, args.version, args.verify_envs, both=args.full_obs) if (args.verify_envs and not dry) else 0
     verified_steps = env.bench_steps_played
     if args.dump_outputs and rk.rank == 0:
         dump_outputs(env, args.dump_outputs)
-    _, (checked, checksum, covered) = rk.reduce([], [checked, outputs_checksum(env) if not dry else 0, n])
+    _, (checked, checksum, covered) = rk.reduce([], [checked, outputs_checksum(env) if (args.full and not dry) else 0, n])
     in_place, two_chains, no_settle = None, None, None
     per_step = b_min(v, args.full_obs, rec_bytes, fused)
     if 'no_settle' in legs_on:
@@ -1061,7 +1075,7 @@ def run_rank(args):      # noqa: C901
                        # the slowest / fastest rank's own K steps (no waiting for the others): weak scaling without a data-path
                        # collective loses nothing as long as these stay at the 1-GPU rate of the same games-per-GPU size
                        "per_gpu_value_min": n * args.steps / own[1], "per_gpu_value_max": n * args.steps / own[0],
-                       "outputs_checksum": checksum,
+                       "outputs_checksum": checksum if args.full else None,
                        # sgx_alloc_outputs' report: observe-launch time on the plain first allocation and on the candidate it kept
                        "placement": placement},
             "roofline": rf,

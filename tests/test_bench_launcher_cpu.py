@@ -85,7 +85,7 @@ def test_self_launch_eight_ranks_with_the_default_workloads_is_self_anchoring():
     alone, the others parked) and scaling_x = value / solo value.  One rank's nccl failure is simulated on top: all eight agree on gloo."""
     import time
     t0 = time.perf_counter()
-    p = _run(['--gpus', '8', '--dry-run', '--backend', 'nccl', '--steps', '3', '--warmup', '1'],
+    p = _run(['--gpus', '8', '--dry-run', '--full', '--backend', 'nccl', '--steps', '3', '--warmup', '1'],
              env=_clean_env(SGX_BENCH_FAKE_NCCL='1', SGX_BENCH_FAIL_NCCL_RANKS='5'), timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     # the whole 8-rank line -- start of the ranks, rendezvous, agreement on the backend after one rank's failure, headline, anchors, config 5
@@ -108,7 +108,7 @@ def test_self_launch_eight_ranks_with_the_default_workloads_is_self_anchoring():
     assert leg['games_per_gpu'] == 262144 and leg['total_games'] == 2097152 and leg['scaling'] == 'weak' and leg['output_sets'] == 1
     assert leg['solo']['games'] == 262144 and leg['scaling_x'] > 0 and leg['per_gpu_value_min_over_solo'] > 0
     # the strong split of the same total over 8 ranks, and one that does not divide evenly
-    p = _run(['--gpus', '8', '--dry-run', '--steps', '2', '--warmup', '1', '--total-envs', '2097152'], timeout=600)
+    p = _run(['--gpus', '8', '--dry-run', '--full', '--steps', '2', '--warmup', '1', '--total-envs', '2097152'], timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _json_lines(p.stdout)[0]
     assert d['scaling'] == 'strong' and d['config']['games_per_gpu'] == 262144 and d['config']['games_covered_by_ranks'] == 2097152
@@ -174,14 +174,14 @@ def test_measured_run_refuses_to_run_without_a_gpu():
 
 def test_defaults_follow_the_baseline_configs_and_the_parent_never_loads_torch():
     """65,536 games per GPU (BASELINE config 2) on any number of GPUs -- the same per-GPU workload, so that `value` over the GPU counts
-    is one curve -- with config 5 (262,144 per GPU) and the strong split of 2,097,152 games as legs of a multi-GPU line, each with its
-    solo anchor; the launcher parent counts GPUs from sysfs without importing torch."""
-    p = _run(['--gpus', '1', '--dry-run', '--steps', '2', '--warmup', '1'])
+    is one curve -- with config 5 (262,144 per GPU) and the strong split of 2,097,152 games as legs of a --full multi-GPU line, each with
+    its solo anchor; the launcher parent counts GPUs from sysfs without importing torch."""
+    p = _run(['--gpus', '1', '--dry-run', '--full', '--steps', '2', '--warmup', '1'])
     assert p.returncode == 0, p.stderr
     d = _json_lines(p.stdout)[0]
     assert d['config']['games_per_gpu'] == 65536 and d['config']['strong_leg_total_games'] == 0 and d['config']['output_sets'] == 3
     assert d['config']['solo'] is None and d['config']['scaling_x'] is None and d['config']['scaling_legs'] is None
-    p = _run(['--gpus', '2', '--dry-run', '--steps', '2', '--warmup', '1'])
+    p = _run(['--gpus', '2', '--dry-run', '--full', '--steps', '2', '--warmup', '1'])
     assert p.returncode == 0, p.stderr
     d = _json_lines(p.stdout)[0]
     c = d['config']
@@ -197,17 +197,41 @@ def test_defaults_follow_the_baseline_configs_and_the_parent_never_loads_torch()
 
 def test_only_rank_0_of_a_one_gpu_run_takes_the_single_gpu_legs():
     """legs_for: the CPU baseline, the live counter passes, the store probe, the facade, the other workloads and the trajectory leg run on
-    rank 0 of a ONE-GPU run and nowhere else; every rank of a multi-GPU job runs the same (barrier-carrying) legs, so nobody waits at a
-    barrier for a rank that is busy elsewhere."""
+    rank 0 of a ONE-GPU --full run and nowhere else; every rank of a multi-GPU job runs the same (barrier-carrying) legs, so nobody waits at
+    a barrier for a rank that is busy elsewhere."""
     import bench
     solo_only = {'cpu_baseline', 'live_traffic', 'store_probe', 'facade_n1', 'other_workloads', 'consumer_in_loop', 'trajectory', 'in_place', 'two_chains'}
-    a1 = bench.parse_args(['--gpus', '1'])
+    a1 = bench.parse_args(['--gpus', '1', '--full'])
     assert solo_only <= bench.legs_for(0, 1, a1) and 'scaling_legs' not in bench.legs_for(0, 1, a1)
     for world in (2, 4, 8):
-        a = bench.parse_args(['--gpus', str(world)])
+        a = bench.parse_args(['--gpus', str(world), '--full'])
         per_rank = [bench.legs_for(r, world, a) for r in range(world)]
         assert all(l == per_rank[0] for l in per_rank), world            # the same legs on every rank
         assert not (per_rank[0] & solo_only) and 'scaling_legs' in per_rank[0] and {'no_settle', 'one_launch_per_step'} <= per_rank[0]
         assert bench.legs_for(3 % world, world, a, dry=True) == {'scaling_legs'}
-    a = bench.parse_args(['--gpus', '1', '--no-cpu-baseline', '--no-other-workloads', '--no-live-traffic', '--no-store-probe', '--no-facade-leg'])
+    a = bench.parse_args(['--gpus', '1', '--full', '--no-cpu-baseline', '--no-other-workloads', '--no-live-traffic', '--no-store-probe', '--no-facade-leg'])
     assert not (bench.legs_for(0, 1, a) & {'cpu_baseline', 'live_traffic', 'store_probe', 'facade_n1', 'other_workloads', 'trajectory'})
+
+
+def test_a_plain_run_is_the_headline_alone():
+    """Without --full a run does only what its headline needs: no leg on any rank, no oracle check, no solo anchor, no outputs checksum;
+    a scaling leg or a verification asked for by size still runs, and --full gives back the default line of every leg."""
+    import bench
+    for world in (1, 2, 8):
+        a = bench.parse_args(['--gpus', str(world)])
+        assert a.verify_envs == 0 and a.leg_envs == 0 and a.strong_total == 0
+        assert all(bench.legs_for(r, world, a) == set() for r in range(world)), world
+        assert bench.legs_for(0, world, a, dry=True) == set()
+    a = bench.parse_args(['--gpus', '2', '--leg-envs', '8192', '--verify-envs', '16'])
+    assert bench.legs_for(1, 2, a) == {'scaling_legs'} and a.verify_envs == 16
+    a = bench.parse_args(['--gpus', '2', '--full'])
+    assert a.verify_envs == 32 and a.leg_envs == 262144 and a.strong_total == 2097152
+    p = _run(['--gpus', '2', '--dry-run', '--steps', '2', '--warmup', '1'])
+    assert p.returncode == 0, p.stderr
+    d = _json_lines(p.stdout)[0]
+    c = d['config']
+    assert d['n_gpus'] == 2 and c['games_covered_by_ranks'] == 131072 and c['stub_steps_x_games'] == 2 * 131072
+    assert c['legs_of_this_line'] == [] and c['solo'] is None and c['scaling_x'] is None and c['scaling_legs'] is None
+    assert c['strong_leg_total_games'] == 0 and c['outputs_checksum'] is None and d['verified_envs'] == 0 and d['cpu_baseline'] is None
+    assert d['metric'] == 'env steps/sec' and d['unit'] == 'env steps/s' and d['higher_is_better'] is True and d['dtype'] == 'u8'
+    assert d['ms_per_step'] > 0

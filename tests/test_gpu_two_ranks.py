@@ -26,7 +26,7 @@ def _run(args, timeout=600, extra_env=None):
     return lines[0]
 
 
-COMMON = ['--steps', '24', '--warmup', '6', '--no-cpu-baseline', '--no-other-workloads', '--verify-envs', '16', '--placement', 'plain',
+COMMON = ['--full', '--steps', '24', '--warmup', '6', '--no-cpu-baseline', '--no-other-workloads', '--verify-envs', '16', '--placement', 'plain',
           '--wake-seconds', '0', '--no-live-traffic', '--no-store-probe', '--no-facade-leg']
 
 
@@ -152,7 +152,7 @@ def test_live_counter_traffic_of_the_headline():
     """roofline.traffic is measured in the run itself: two short children of bench.py under rocprofv3 --pmc (FETCH_SIZE, WRITE_SIZE), the
     guide's gfx950 correction; it must agree with the byte minimum of the launch (the kernel moves its minimum and little else) and the
     static entry of profiles/traffic.json stays next to it."""
-    line = _run(['--gpus', '1', '--envs', '16384', '--steps', '12', '--warmup', '4', '--no-cpu-baseline', '--no-other-workloads', '--no-two-chains',
+    line = _run(['--gpus', '1', '--full', '--envs', '16384', '--steps', '12', '--warmup', '4', '--no-cpu-baseline', '--no-other-workloads', '--no-two-chains',
                  '--no-in-place-leg', '--no-settle-leg', '--verify-envs', '8', '--placement', 'plain', '--wake-seconds', '0'], timeout=900)
     rf = line['roofline']
     assert 'traffic_live_failed' not in rf, rf.get('traffic_live_failed')

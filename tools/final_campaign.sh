@@ -7,9 +7,10 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 mkdir -p gpurun_out/$OUT
+D=$_                                           # the directory just made: where the bench lines go
 python -m pytest tests -m gpu -q > gpurun_out/$OUT/pytest.log 2>&1; echo PYTEST_RC $?; tail -3 gpurun_out/$OUT/pytest.log
-python bench.py > gpurun_out/$OUT/bench_default.json 2> gpurun_out/$OUT/bench_default.err; echo BENCH_RC $?
-python bench.py --steps 20 --warmup 5 > gpurun_out/$OUT/bench_driver_style.json 2> gpurun_out/$OUT/bench_driver_style.err; echo BENCH2_RC $?
+python bench.py --full > $D/bench_default.json 2> $D/bench_default.err; echo BENCH_RC $?
+python bench.py --full --steps 20 --warmup 5 > $D/bench_driver_style.json 2> $D/bench_driver_style.err; echo BENCH2_RC $?
 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/$OUT/smoke.log 2>&1; tail -1 gpurun_out/$OUT/smoke.log
 bash tools/gpu_profile.sh ${RND}_untuned_headline barrage+rotating 65536 > gpurun_out/prof_${RND}_untuned_headline.log 2>&1
 bash tools/gpu_profile.sh ${RND}_inplace barrage 65536 --output-sets 1 > gpurun_out/prof_${RND}_inplace.log 2>&1
@@ -32,7 +33,7 @@ python tools/procedural_bench.py > gpurun_out/$OUT/procedural_bench.log 2>&1
 for v in barrage standard micro tiny fives; do python tools/phase_cost.py $v 65536 2>&1 | grep -v "^/opt"; done > gpurun_out/$OUT/phase_cost.log
 python tools/multi_step_ab.py 2>&1 | grep -v "^/opt" > gpurun_out/$OUT/multi_step_ab.log
 python tools/ring_size_probe_tuned.py 2>&1 | grep -v "^/opt" > gpurun_out/$OUT/ring_size_probe_tuned.log
-for i in 2 3; do python bench.py > gpurun_out/$OUT/bench_default_run$i.json 2> gpurun_out/$OUT/bench_default_run$i.err; done
+for i in 2 3; do python bench.py --full > $D/bench_default_run$i.json 2> $D/bench_default_run$i.err; done
 python -W ignore tools/half_wave_ab.py barrage standard octa_barrage medium 2>&1 | grep -v "^/opt" > gpurun_out/$OUT/half_wave_ab.log
 python tools/noobs_small_ab.py 2>&1 | grep -v "^/opt" > gpurun_out/$OUT/noobs_small_ab.log
 python tools/r06_spread_probe.py 2>&1 | grep -v "^/opt" > gpurun_out/$OUT/spread_probe.log

@@ -94,6 +94,45 @@ typedef struct sgx_step_io {
     int32_t flags;                 /* SGX_STEP_* bits, 0 for the env.step() path */
 } sgx_step_io;
 
+/* Alignment of device pointers.  What each pointer needs follows from the widest store (or load) a kernel issues through it; every entry
+ * point checks its pointers on the host BEFORE it launches anything and returns SGX_EINVAL with a message that names the pointer and the
+ * alignment ("sgx_step: obs_dev must be 16-byte aligned").  A pointer that passes is handled at every phase it can then have:
+ * tests/test_gpu_guard_bands.py runs each kernel family with its tensors at those phases between guard bands and finds no byte written
+ * outside them.  "Quad boards" are those whose cell count rows*cols is a multiple of 4 (10x10, 8x8, 6x6, 4x4, 3x4), "odd boards" the rest
+ * (15x15, 5x5).  Members of sgx_step_io, for sgx_step, sgx_step_sync, sgx_observe (its arguments of the same names), sgx_step_n,
+ * sgx_step_ring (every set), sgx_step_traj (slot 0; the slots behind it are then as aligned), sgx_rollout, sgx_expand, sgx_step_states:
+ *   actions_dev          4   (16 with SGX_STEP_ACTIONS_POSITIONS: one 16-byte load per game)
+ *   next_actions_dev     4
+ *   obs_dev              16 on quad boards (16-byte stores at 16-byte steps from the pointer), 4 on odd boards (any float phase: the
+ *                        kernels write the partial first / last 16 bytes of a game as single floats); 16 with SGX_STEP_COMPACT_OBS
+ *   fobs_dev             as obs_dev
+ *   final_obs_dev        as obs_dev
+ *   final_fobs_dev       as obs_dev
+ *   mask_dev             1   (any address, on every board and for SGX_STEP_MASK_1D / SGX_STEP_MASK_STATE_COORDS: partial 16-byte chunks
+ *                        of a game leave byte by byte unless the pointer is 4-byte aligned); 16 with SGX_STEP_COMPACT_MASK
+ *   reward_dev           4
+ *   done_dev             1
+ *   player_dev           1
+ *   invalid_action_dev   1
+ *   ending_invalid_dev   1
+ * The multi-step launches of the one-game-per-lane kernel (sgx_set_lane_kernel) additionally want 16-byte aligned obs_dev, mask_dev and
+ * actions_dev and an 8-byte aligned reward_dev; a call that misses this is not an error: the wave-per-game kernels play it, with the same
+ * results.  Other entry points:
+ *   sgx_traj_io.actions_log_dev                               4
+ *   sgx_decode_obs       compact_dev 16; obs_dev as above (16 on quad boards, 4 on odd boards)
+ *   sgx_decode_mask      bits_dev 16; mask_dev 1
+ *   sgx_sample_valid     mask_dev 1; actions_dev 4
+ *   sgx_choose_actions   logits_dev 4; mask_dev 1 (4 with SGX_STEP_COMPACT_MASK); actions_dev 4
+ *   sgx_export_state / sgx_import_state / sgx_import_state_checked / sgx_step_states:
+ *                        state_dev, state_in_dev, state_out_dev 16 (the int64 layers travel as 16-byte loads / stores);
+ *                        player_dev, player_in_dev, player_out_dev, sanitised_dev 1
+ *   sgx_get_env_info     info_dev 16 (one 16-byte store per game)
+ *   sgx_reset            env_select_dev, p1_maps_dev, p2_maps_dev 1
+ *   sgx_expand / sgx_copy_envs   src_index_dev, dst_index_dev 4
+ *   sgx_mem_probe        ptr_dev 1024;   sgx_store_probe   ptr_dev 16
+ * Change note: these rejections are new error returns for pointers that were never legal (the stores they guard were issued unchecked
+ * before; only sgx_decode_obs and the compact path refused them); no struct or signature changed, so SGX_ABI_VERSION stays. */
+
 /* sgx_step_io.flags: the functional StrategoProceduralEnv API on caller-provided states (import -> step -> export) */
 #define SGX_STEP_ACTIONS_1D 1         /* actions_dev holds absolute-coordinate 1-D indices (impl:262-277), as
                                          get_next_state / is_move_valid_by_1d_index take them (penv:94-99, 148-155) */
@@ -452,7 +491,9 @@ int sgx_import_state_checked(sgx_env *h, const int64_t *state_dev, const int8_t 
  * NO ALIASING while the general-state pass is on (the default, see sgx_set_general_states; boards of up to 256 cells): that pass reads
  * state_in_dev / player_in_dev again after the outputs have been written, so state_out_dev must not overlap state_in_dev and
  * player_out_dev must not overlap player_in_dev -- SGX_EINVAL otherwise.  With the pass off, stepping a batch in place is fine (every
- * state is read completely before its successor is written). */
+ * state is read completely before its successor is written): state_out_dev == state_in_dev, player_out_dev == player_in_dev.  Any OTHER
+ * overlap (outputs shifted against the inputs by some states) is SGX_EINVAL in either mode: one workgroup would write what another has
+ * yet to read. */
 int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_t *player_in_dev, uint8_t *sanitised_dev,
                     const sgx_step_io *io, int64_t *state_out_dev, int8_t *player_out_dev, int32_t chains, void *stream);
 

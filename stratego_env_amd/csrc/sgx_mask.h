@@ -157,13 +157,24 @@ __device__ void emit_mask(const Lds<G, NB> &L, uint8_t *__restrict__ dst, int la
             const uint32_t b16 = mask_bits(L, lo, 16);
             i32x4 q4 = {(int)expand4(b16 & 15), (int)expand4((b16 >> 4) & 15), (int)expand4((b16 >> 8) & 15), (int)expand4(b16 >> 12)};
             reinterpret_cast<i32x4 *>(gbase)[c] = q4;
-        } else if constexpr (G::NA % 4 == 0) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int o = lo + 4 * w;
-                if (o >= 0 && o < G::NA) *reinterpret_cast<uint32_t *>(dst + o) = expand4(mask_bits(L, o, 4));
-            }
         } else {
+            // dwords only where every dword of the chunk lies wholly inside or wholly outside the mask: NA a multiple of 4 AND a
+            // 4-byte aligned base.  (With a = A & 3 != 0 the dword at o = -a was skipped, leaving bytes 0 .. 3 - a unwritten, and the one
+            // at o = NA - a was stored whole, 4 - a bytes past the game's mask: tests/test_gpu_guard_bands.py, uint8 phases 1-3.)
+            if constexpr (G::NA % 4 == 0) {
+#ifdef SGX_MUTANT_MASK_DWORDS   // tools/mutant_check.sh: the code before the fix
+                if (true) {
+#else
+                if ((A & 3) == 0) {
+#endif
+#pragma unroll
+                    for (int w = 0; w < 4; ++w) {
+                        const int o = lo + 4 * w;
+                        if (o >= 0 && o < G::NA) *reinterpret_cast<uint32_t *>(dst + o) = expand4(mask_bits(L, o, 4));
+                    }
+                    continue;
+                }
+            }
             for (int o = max(lo, 0); o < min(lo + 16, (int)G::NA); ++o) dst[o] = (uint8_t)((L.mbits[o >> 5] >> (o & 31)) & 1u);
         }
     }

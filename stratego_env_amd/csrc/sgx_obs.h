@@ -205,7 +205,11 @@ __device__ inline void emit_codes(const Lds<G, NB> &L, float *__restrict__ dst, 
         const int first_line = l0 ? 0 : -1, last_line = ((l0 + NQ) & 7) ? (NQ - 1 + l0) >> 3 : -1;   // lines counted from dst - 16 * l0
         auto sweep = [&](const int q0) __attribute__((always_inline)) {
             const int q = q0 + lane;
+#ifdef SGX_MUTANT_OBS_QUAD_OVER   // tools/mutant_check.sh: one quad (16 bytes) past every game's observation
+            const bool in = (unsigned)q <= (unsigned)NQ;
+#else
             const bool in = (unsigned)q < (unsigned)NQ;
+#endif
             const unsigned x = n16[in ? q : 0];
             f32x4 o = {code_to_float(x), code_to_float(x >> 4), code_to_float(x >> 8), code_to_float(x >> 12)};
             bool esc = false;
@@ -261,7 +265,11 @@ __device__ inline void emit_codes(const Lds<G, NB> &L, float *__restrict__ dst, 
             const unsigned x = w >> sh;
             const float o[4] = {code_to_float(x), code_to_float(x >> 4), code_to_float(x >> 8), code_to_float(x >> 12)};
             const int f0 = 4 * kk - a;
+#ifdef SGX_MUTANT_OBS_LAST_SLOT_WHOLE   // tools/mutant_check.sh: the partial last slot as one 16-byte store (up to 3 floats past the game)
+            if (slot_in && f0 >= 0) {
+#else
             if (slot_in && f0 >= 0 && f0 + 3 < NF) {
+#endif
                 f32x4 qv = {o[0], o[1], o[2], o[3]};
                 const int line = (k + l0) >> 3;
                 // (sending the lines that hold an uncoded entry through L2, like the 4-aligned boards do, measured 11 % SLOWER here:

@@ -685,6 +685,39 @@ static int check_step_io(sgx_env *h, const KParams &p) {
     return SGX_OK;
 }
 
+// The pointer contract of include/stratego_mi355x.h ("Alignment of device pointers"), checked by every entry point BEFORE it launches
+// anything: a pointer the kernels' stores cannot take is SGX_EINVAL with its name and the alignment it needs, never a launch.
+static int check_aligned(const char *fn, const char *name, const void *ptr, int align) {
+    if ((reinterpret_cast<uintptr_t>(ptr) & (uintptr_t)(align - 1)) == 0) return SGX_OK;       // (NULL passes: nullable or refused elsewhere)
+    char buf[160];
+    snprintf(buf, sizeof(buf), "%s: %s must be %d-byte aligned", fn, name, align);
+    return fail(SGX_EINVAL, "%s", buf);
+}
+// Every *_dev member of sgx_step_io (tests/test_cabi_cpu.py holds this table against the struct and the header's contract).  Observations
+// leave as 16-byte stores on boards whose cell count is a multiple of 4 (emit_codes / emit_obs_lut / patch_uncoded: f32x4 at dst + 16 q), as
+// dwords at the edges of a game on the others; compact outputs are int4 copies; position actions are one int4 load per game; the byte
+// outputs are written byte by byte wherever a dword would not be the caller's (emit_mask, emit_mask_mapped).
+static int check_io_pointers(const sgx_env *h, const sgx_step_io &io, const char *fn) {
+    const int quad = (h->cfg.rows * h->cfg.cols) % 4 == 0 ? 16 : 4;
+    const struct { const char *name; const void *ptr; int align; } tab[] = {
+        {"actions_dev", io.actions_dev, (io.flags & SGX_STEP_ACTIONS_POSITIONS) ? 16 : 4},
+        {"obs_dev", io.obs_dev, (io.flags & SGX_STEP_COMPACT_OBS) ? 16 : quad},
+        {"fobs_dev", io.fobs_dev, quad},
+        {"mask_dev", io.mask_dev, (io.flags & SGX_STEP_COMPACT_MASK) ? 16 : 1},
+        {"reward_dev", io.reward_dev, 4},
+        {"done_dev", io.done_dev, 1},
+        {"player_dev", io.player_dev, 1},
+        {"invalid_action_dev", io.invalid_action_dev, 1},
+        {"ending_invalid_dev", io.ending_invalid_dev, 1},
+        {"final_obs_dev", io.final_obs_dev, quad},
+        {"final_fobs_dev", io.final_fobs_dev, quad},
+        {"next_actions_dev", io.next_actions_dev, 4},
+    };
+    for (const auto &e : tab)
+        if (int rc = check_aligned(fn, e.name, e.ptr, e.align)) return rc;
+    return SGX_OK;
+}
+
 // The output sets of a rollout call: sgx_step_n (one set, in place), sgx_step_ring (n_sets separate sets: ios[0 .. n_sets)), or the slots of
 // an sgx_step_traj trajectory buffer (strided: ios[0] names slot 0, slot s lies s x the byte strides further; KParams::traj_* carry the
 // strides of the per-step results and of the action log).
@@ -1039,6 +1072,7 @@ SGX_API int sgx_observe(sgx_env *h, float *obs_dev, float *fobs_dev, uint8_t *ma
     p.io.flags = flags & (SGX_STEP_RAW_OBS | SGX_STEP_ORIGINAL_CHANNELS | SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS | SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK);
     p.io.mask_dev = mask_dev;
     p.io.player_dev = player_dev;
+    if (int rc = check_io_pointers(h, p.io, "sgx_observe")) return rc;
     return launch_step(h, p, stream);
 }
 
@@ -1289,6 +1323,7 @@ SGX_API int sgx_alloc_outputs(sgx_env *h, int32_t flags, int64_t max_extra_bytes
 SGX_API int sgx_step(sgx_env *h, const sgx_step_io *io, void *stream) {
     if (!h || !io) return fail(SGX_EINVAL, "handle or io is NULL%s");
     if (!io->actions_dev) return fail(SGX_EINVAL, "actions_dev is NULL%s");
+    if (int rc = check_io_pointers(h, *io, "sgx_step")) return rc;
     SGX_ON_DEVICE(h->device);
     KParams p = make_params(h);
     p.mode = 0;
@@ -1391,6 +1426,7 @@ int step_single(sgx_env *h, const KParams &p, bool full, hipStream_t stream, boo
 SGX_API int sgx_step_sync(sgx_env *h, const sgx_step_io *io, void *stream) {
     if (!h || !io) return fail(SGX_EINVAL, "handle or io is NULL%s");
     if (!io->actions_dev) return fail(SGX_EINVAL, "actions_dev is NULL%s");
+    if (int rc = check_io_pointers(h, *io, "sgx_step_sync")) return rc;
     const bool original = (io->flags & SGX_STEP_ORIGINAL_CHANNELS) != 0;
     if (h->n_envs <= SGX_SINGLE_MAX_ENVS && !original && !(io->flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS | SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) && h->map_mode == 0 &&
         !h->no_single) {
@@ -1441,6 +1477,7 @@ SGX_API int sgx_step_n(sgx_env *h, const sgx_step_io *io, int32_t n_steps, void 
     if (!io->actions_dev || io->next_actions_dev != io->actions_dev)
         return fail(SGX_EINVAL, "sgx_step_n needs next_actions_dev == actions_dev (each step plays the action the previous one drew)%s");
     if (n_steps < 0) return fail(SGX_EINVAL, "n_steps is negative%s");
+    if (int rc = check_io_pointers(h, *io, "sgx_step_n")) return rc;
     SGX_ON_DEVICE(h->device);
     KParams p = make_params(h);
     p.mode = 0;
@@ -1456,6 +1493,7 @@ SGX_API int sgx_step_ring(sgx_env *h, const sgx_step_io *ios, int32_t n_sets, in
             return fail(SGX_EINVAL, "sgx_step_ring: every set needs next_actions_dev == actions_dev == the first set's (each step plays the action the previous one drew)%s");
         if (ios[k].auto_reset != ios[0].auto_reset || ios[k].flags != ios[0].flags)
             return fail(SGX_EINVAL, "sgx_step_ring: the sets differ in auto_reset or flags%s");
+        if (int rc = check_io_pointers(h, ios[k], "sgx_step_ring")) return rc;
     }
     SGX_ON_DEVICE(h->device);
     KParams p = make_params(h);
@@ -1471,6 +1509,10 @@ SGX_API int sgx_step_traj(sgx_env *h, const sgx_traj_io *t, int32_t first_slot, 
         return fail(SGX_EINVAL, "sgx_step_traj needs next_actions_dev == actions_dev (each step plays the action the previous one drew)%s");
     if (t->n_slots < 1 || first_slot < 0 || first_slot >= t->n_slots || n_steps < 0) return fail(SGX_EINVAL, "sgx_step_traj: n_slots, first_slot or n_steps out of range%s");
     if (t->slot_envs < h->n_envs) return fail(SGX_EINVAL, "sgx_step_traj: slot_envs is smaller than the number of envs%s");
+    // (slot s of a tensor lies s x slot_envs games further: as aligned as slot 0 wherever slot 0 passes -- a game's float32 observation is a
+    // multiple of 16 bytes on the boards that need 16, compact records are padded to 128 bytes and the bit masks to 16)
+    if (int rc = check_io_pointers(h, io, "sgx_step_traj")) return rc;
+    if (int rc = check_aligned("sgx_step_traj", "actions_log_dev", t->actions_log_dev, 4)) return rc;
     SGX_ON_DEVICE(h->device);
     KParams p = make_params(h);
     p.mode = 0;
@@ -1494,6 +1536,7 @@ SGX_API int sgx_rollout(sgx_env *h, const sgx_step_io *io, int32_t n_steps, int3
     if (!io->actions_dev || io->next_actions_dev != io->actions_dev)
         return fail(SGX_EINVAL, "sgx_rollout needs next_actions_dev == actions_dev (each step plays the action the previous one drew)%s");
     if (n_steps < 0 || chains < 0 || chains > SGX_MAX_CHAINS) return fail(SGX_EINVAL, "n_steps or chains out of range%s");
+    if (int rc = check_io_pointers(h, *io, "sgx_rollout")) return rc;
     // games per chain: a multiple of what eight workgroups play, so that every chain keeps the XCD-aware map
     const int cells = h->cfg.rows * h->cfg.cols;
     // chains = 0: the measured rule (profiles/r04_variant_bench.log, 65,536 games in place): two chains gain where one launch leaves
@@ -1542,6 +1585,7 @@ SGX_API int sgx_decode_obs(sgx_env *h, const uint8_t *compact_dev, float *obs_de
     if (reinterpret_cast<uintptr_t>(compact_dev) & 15) return fail(SGX_EINVAL, "sgx_decode_obs: compact_dev must be 16-byte aligned%s");
     if ((reinterpret_cast<uintptr_t>(obs_dev) & 15) && (h->cfg.rows * h->cfg.cols) % 4 == 0)
         return fail(SGX_EINVAL, "sgx_decode_obs: obs_dev must be 16-byte aligned%s");
+    if (int rc = check_aligned("sgx_decode_obs", "obs_dev", obs_dev, 4)) return rc;
     SGX_ON_DEVICE(h->device);
     const int nt = nt_for(h, h->n_envs * (int64_t)h->cfg.rows * h->cfg.cols * OBS_CH * 4);
     if (int rc = for_geometry(h, [&](auto r, auto c) {
@@ -1570,6 +1614,7 @@ SGX_API int sgx_decode_mask(sgx_env *h, const uint32_t *bits_dev, uint8_t *mask_
 
 SGX_API int sgx_sample_valid(sgx_env *h, const uint8_t *mask_dev, int32_t *actions_dev, void *stream) {
     if (!h || !mask_dev || !actions_dev) return fail(SGX_EINVAL, "NULL argument%s");
+    if (int rc = check_aligned("sgx_sample_valid", "actions_dev", actions_dev, 4)) return rc;
     SGX_ON_DEVICE(h->device);
     KParams p = make_params(h);
     if (int rc = for_geometry(h, [&](auto r, auto c) {
@@ -1587,6 +1632,7 @@ SGX_API int sgx_choose_actions(sgx_env *h, const float *logits_dev, const void *
     const bool bits = (flags & SGX_STEP_COMPACT_MASK) != 0;
     if ((reinterpret_cast<uintptr_t>(logits_dev) & 3) || (bits && (reinterpret_cast<uintptr_t>(mask_dev) & 3)))
         return fail(SGX_EINVAL, "sgx_choose_actions: logits_dev (and a compact mask_dev) must be 4-byte aligned%s");
+    if (int rc = check_aligned("sgx_choose_actions", "actions_dev", actions_dev, 4)) return rc;
     SGX_ON_DEVICE(h->device);
     const KParams p = make_params(h);
     const float scale = temperature == 0.f ? __builtin_inff() : 1.4426950408889634f / temperature;     // (+inf: every weight below the maximum's is 0)
@@ -1652,12 +1698,14 @@ int launch_import(sgx_env *h, const KParams &p_in, const int64_t *state_dev, con
 
 SGX_API int sgx_export_state(sgx_env *h, int64_t *state_dev, int8_t *player_dev, void *stream) {
     if (!h || !state_dev) return fail(SGX_EINVAL, "NULL argument%s");
+    if (int rc = check_aligned("sgx_export_state", "state_dev", state_dev, 16)) return rc;
     SGX_ON_DEVICE(h->device);
     return launch_export(h, make_params(h), state_dev, player_dev, (hipStream_t)stream);
 }
 
 SGX_API int sgx_import_state_checked(sgx_env *h, const int64_t *state_dev, const int8_t *player_dev, uint8_t *sanitised_dev, void *stream) {
     if (!h || !state_dev) return fail(SGX_EINVAL, "NULL argument%s");
+    if (int rc = check_aligned("sgx_import_state", "state_dev", state_dev, 16)) return rc;
     SGX_ON_DEVICE(h->device);
     return launch_import(h, make_params(h), state_dev, player_dev, sanitised_dev, (hipStream_t)stream);
 }
@@ -1692,6 +1740,9 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
     if (io->auto_reset || io->next_actions_dev) return fail(SGX_EINVAL, "sgx_step_states: no auto_reset, no sampled next actions%s");
     if (io->flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) return fail(SGX_EINVAL, "sgx_step_states: no compact outputs%s");
     if (chains < 1 || chains > SGX_MAX_CHAINS) return fail(SGX_EINVAL, "chains out of range%s");
+    if (int rc = check_io_pointers(h, *io, "sgx_step_states")) return rc;
+    if (int rc = check_aligned("sgx_step_states", "state_in_dev", state_in_dev, 16)) return rc;      // (16-byte loads / stores of the int64 layers)
+    if (int rc = check_aligned("sgx_step_states", "state_out_dev", state_out_dev, 16)) return rc;
     const int cells = h->cfg.rows * h->cfg.cols;
     const bool kind0 = !io->fobs_dev && !io->final_fobs_dev && !(io->flags & SGX_STEP_ORIGINAL_CHANNELS);
     const bool mapped = (io->flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) != 0;
@@ -1704,17 +1755,25 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
     // block of that launch leaves at once.  Not: boards of more than 256 cells; state-coordinate masks together with another observation
     // kind (which the fused path does not take).
     const bool general = h->general_states != 0 && cells <= 256 && (kind0 || !mapped);
+    auto overlap = [](const void *a, int64_t na, const void *b, int64_t nb) {
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+        return a && b && a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
+    };
+    const bool states_overlap = overlap(state_in_dev, state_bytes(h), state_out_dev, state_bytes(h));
+    const bool players_overlap = overlap(player_in_dev, h->n_envs, player_out_dev, h->n_envs);
     if (general) {
         // The general-state pass re-reads the caller's INPUT after the first pass has written the outputs: a state stepped in place would
-        // be redone from its own successor (stepped twice, or judged invalid) without anybody noticing.  (Calls behind which no such pass
-        // runs may step a batch in place: every state is read completely before its successor is written.)
-        auto overlap = [](const void *a, int64_t na, const void *b, int64_t nb) {
-            const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-            return a && b && a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
-        };
-        if (overlap(state_in_dev, state_bytes(h), state_out_dev, state_bytes(h)) || overlap(player_in_dev, h->n_envs, player_out_dev, h->n_envs))
+        // be redone from its own successor (stepped twice, or judged invalid) without anybody noticing.
+        if (states_overlap || players_overlap)
             return fail(SGX_EINVAL, "sgx_step_states: state_out_dev / player_out_dev overlap the inputs, which the general-state pass reads again "
                                     "after the outputs are written; pass distinct buffers or switch the pass off (sgx_set_general_states(h, 0))%s");
+    } else {
+        // No second pass: a batch may be stepped IN PLACE (state_out_dev == state_in_dev, player_out_dev == player_in_dev: the workgroup of
+        // state i reads state i completely before it writes its successor, and touches no other state).  Any other overlap -- outputs
+        // shifted by some states against the inputs -- makes one workgroup write what another one has yet to read.
+        if ((states_overlap && state_out_dev != state_in_dev) || (players_overlap && player_out_dev != player_in_dev))
+            return fail(SGX_EINVAL, "sgx_step_states: state_out_dev / player_out_dev overlap the inputs without being the same pointers "
+                                    "(in place is fine with the general-state pass off; a shifted overlap races between workgroups)%s");
     }
     SGX_ON_DEVICE(h->device);
     const int64_t unit = 64;
@@ -1836,6 +1895,8 @@ SGX_API int sgx_copy_envs(sgx_env *dst, const int32_t *dst_index_dev, sgx_env *s
     if (dst == src && (dst_index_dev || src_index_dev))
         return fail(SGX_EINVAL, "sgx_copy_envs: an indexed copy inside one handle would race; stage through a second handle%s");
     if (n == 0 || dst == src) return SGX_OK;
+    if (int rc = check_aligned("sgx_copy_envs", "dst_index_dev", dst_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_copy_envs", "src_index_dev", src_index_dev, 4)) return rc;
     SGX_ON_DEVICE(dst->device);
     copy_records_kernel<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(dst->boards, dst_index_dev, src->boards, src_index_dev, dst->rec_bytes, n);
     HIP_TRY(hipGetLastError());
@@ -1854,6 +1915,8 @@ SGX_API int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
     if (io->auto_reset) return fail(SGX_EINVAL, "sgx_expand does not auto-reset%s");
     if (io->fobs_dev || io->final_fobs_dev || (io->flags & SGX_STEP_ORIGINAL_CHANNELS))
         return fail(SGX_EINVAL, "sgx_expand renders the 67-channel partial observation only%s");
+    if (int rc = check_io_pointers(dst, *io, "sgx_expand")) return rc;
+    if (int rc = check_aligned("sgx_expand", "src_index_dev", src_index_dev, 4)) return rc;
     SGX_ON_DEVICE(dst->device);
     KParams p = make_params(dst);
     p.mode = 0;
@@ -1865,6 +1928,7 @@ SGX_API int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
 
 SGX_API int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream) {
     if (!h || !info_dev) return fail(SGX_EINVAL, "NULL argument%s");
+    if (int rc = check_aligned("sgx_get_env_info", "info_dev", info_dev, 16)) return rc;      // (info_kernel: one int4 store per game)
     SGX_ON_DEVICE(h->device);
     info_kernel<<<(unsigned)((h->n_envs + 255) / 256), 256, 0, (hipStream_t)stream>>>(h->boards, h->rec_bytes, h->sc_off, info_dev, h->n_envs);
     HIP_TRY(hipGetLastError());

@@ -574,12 +574,25 @@ class VecStrategoEnv:
         T = int(traj['obs'].shape[0])
         if not 0 <= first_slot < T:
             raise ValueError("first_slot out of range")
-        for k in ('obs', 'mask'):
-            if tuple(traj[k].shape[1:]) != tuple(getattr(self, k).shape) or traj[k].dtype != getattr(self, k).dtype or not traj[k].is_contiguous():
-                raise ValueError("traj['%s'] must be a contiguous [T, %s] %s tensor" % (k, ', '.join(map(str, getattr(self, k).shape)), getattr(self, k).dtype))
         if (self.fobs is not None) != ('fobs' in traj):
             raise ValueError("traj['fobs'] goes with full_obs=True")
         per_slot = 'reward' in traj
+        # every tensor of the dict reaches sgx_step_traj as a raw pointer with ONE slot stride (num_envs): all of them are checked here,
+        # before anything is launched or any tensor of the env is swapped
+        N = self.num_envs
+        want = {'obs': (tuple(self.obs.shape), self.obs.dtype), 'mask': (tuple(self.mask.shape), self.mask.dtype)}
+        if 'fobs' in traj:
+            want['fobs'] = (tuple(self.fobs.shape), torch.float32)
+        if per_slot:
+            want.update({'reward': ((N, 2), torch.float32), 'done': ((N,), torch.uint8), 'player': ((N,), torch.int8),
+                         'invalid_action': ((N,), torch.uint8), 'ending_invalid': ((N,), torch.uint8)})
+        if 'actions' in traj:
+            want['actions'] = ((N,), torch.int32)
+        for k, (shape, dtype) in want.items():
+            t = traj.get(k)
+            if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (T,) + shape or t.dtype != dtype or not t.is_contiguous() or t.device != self.device):
+                raise ValueError("traj['%s'] must be a contiguous [%d, %s] %s tensor on %s (alloc_trajectory makes them)"
+                                 % (k, T, ', '.join(map(str, shape)), dtype, self.device))
         if not self._next_actions_fresh:
             self.sample_valid_actions()
         keep = (self.obs, self.mask, self.fobs, self.reward, self.done, self.player, self.invalid_action, self.ending_invalid)

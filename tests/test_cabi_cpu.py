@@ -238,3 +238,40 @@ def test_missing_library_fails_loudly():
     with pytest.raises(_lib.SgxError) as ei:
         _lib.load('/nonexistent/libstratego_mi355x.so')
     assert 'no CPU fallback' in str(ei.value)
+
+
+def test_every_device_pointer_has_a_line_in_the_alignment_contract():
+    """include/stratego_mi355x.h states the alignment of every device pointer ("Alignment of device pointers"), and the host checks it before
+    any launch (check_io_pointers in stratego_mi355x.hip).  A pointer added to sgx_step_io / sgx_traj_io, or a new *_dev argument of an
+    entry point, without a line in the contract AND (for sgx_step_io members) a row in the host check's table fails here."""
+    hdr = open(os.path.join(ROOT, 'include', 'stratego_mi355x.h')).read()
+    src = open(os.path.join(ROOT, 'stratego_env_amd', 'csrc', 'stratego_mi355x.hip')).read()
+    start = hdr.index('/* Alignment of device pointers.')
+    contract = hdr[start:hdr.index('*/', start)]
+    rest = hdr[:start] + hdr[hdr.index('*/', start):]
+    # the struct's pointer members
+    io = re.search(r'typedef struct sgx_step_io \{(.*?)\} sgx_step_io;', hdr, re.S).group(1)
+    members = re.findall(r'\*\s*(\w+_dev)\s*;', io)
+    assert len(members) == 12 and 'mask_dev' in members and 'final_fobs_dev' in members
+    table = src[src.index('static int check_io_pointers('):]
+    table = table[:table.index('return SGX_OK;')]
+    rows = re.findall(r'\{"(\w+_dev)", io\.(\w+_dev), ', table)
+    assert [a for a, b in rows] == [b for a, b in rows], 'a row of the table names one pointer and checks another'
+    assert sorted(a for a, _ in rows) == sorted(members), 'check_io_pointers and sgx_step_io disagree about the pointers of a step'
+    for m in members:
+        assert re.search(r'^ \*   %s\s+\d' % m, contract, re.M) or re.search(r'^ \*   %s\s+as obs_dev' % m, contract, re.M), \
+            '%s has no line in the alignment contract of the header' % m
+    # every other *_dev name the header declares (arguments of entry points, members of sgx_traj_io / sgx_outputs) is named in the contract
+    declared = set(re.findall(r'\b(\w+_dev)\b', re.sub(r'/\*.*?\*/', '', rest, flags=re.S)))
+    library_owned = set()                                # (sgx_outputs' obs_dev / fobs_dev / mask_dev share the step's names)
+    missing = sorted(d for d in declared - library_owned if not re.search(r'\b%s\b' % d, contract))
+    assert not missing, 'device pointers without a line in the alignment contract: %s' % missing
+    # every stepping entry point runs the check before it launches
+    for fn in ('sgx_step', 'sgx_step_sync', 'sgx_observe', 'sgx_step_n', 'sgx_step_ring', 'sgx_step_traj', 'sgx_rollout', 'sgx_expand', 'sgx_step_states'):
+        body = src[src.index('SGX_API int %s(' % fn):]
+        body = body[:body.index('\n}\n')]
+        at = body.find('check_io_pointers(')
+        assert at >= 0 and '"%s"' % fn in body[at:at + 120], '%s does not check its pointers' % fn
+        launch = min([i for i in (body.find('<<<'), body.find('launch_step('), body.find('play_steps('), body.find('multi_steps('), body.find('step_single('),
+                                  body.find('launch_import('), body.find('fork_chains(')) if i >= 0])
+        assert at < launch, '%s launches before it has checked its pointers' % fn

@@ -9,7 +9,7 @@
  *     (e.g. a torch tensor's data_ptr()); the library owns only its internal state tensor;
  *   - all device work is enqueued on `stream` (a hipStream_t passed as void*, NULL = default stream)
  *     and is asynchronous; the entry points that wait for the device are sgx_create, sgx_destroy,
- *     sgx_set_setup_table, sgx_time_observe, sgx_mem_probe, sgx_store_probe, sgx_step_sync, sgx_host_free, sgx_alloc_outputs and
+ *     sgx_set_setup_table, sgx_set_start_pool, sgx_time_observe, sgx_mem_probe, sgx_store_probe, sgx_step_sync, sgx_host_free, sgx_alloc_outputs and
  *     sgx_free_outputs;
  *   - return 0 on success, a negative SGX_E* code on failure (sgx_last_error() has the text);
  *     nothing throws across the ABI; invalid *actions* are not API errors: they are reported per env
@@ -128,6 +128,7 @@ typedef struct sgx_step_io {
  *                        player_dev, player_in_dev, player_out_dev, sanitised_dev 1
  *   sgx_get_env_info     info_dev 16 (one 16-byte store per game)
  *   sgx_reset            env_select_dev, p1_maps_dev, p2_maps_dev 1
+ *   sgx_set_start_index_out   start_index_dev 4
  *   sgx_expand / sgx_copy_envs   src_index_dev, dst_index_dev 4
  *   sgx_mem_probe        ptr_dev 1024;   sgx_store_probe   ptr_dev 16
  * Change note: these rejections are new error returns for pointers that were never legal (the stores they guard were issued unchecked
@@ -293,8 +294,46 @@ int sgx_set_setup_table(sgx_env *h, const uint8_t *table_host, int64_t n_setups)
 /* reset() (maenv:513-657) for the envs selected by env_select_dev (uint8 [N], NULL = all).
  * p1_maps_dev / p2_maps_dev: int8 [N][R*C] own-side piece maps, the inputs of create_initial_state
  * (penv:38-60 -> impl:211-249); pass NULL for both to sample setups (table or random placement).
- * Starts game number 0 (explicit maps) or the env's next game number (sampled).  Player +1 moves first. */
+ * Starts game number 0 (explicit maps) or the env's next game number (sampled).  Player +1 moves first -- unless the handle has a
+ * start pool (sgx_set_start_pool below): NULL maps then start every selected env from a pool record, with that record's first mover. */
 int sgx_reset(sgx_env *h, const uint8_t *env_select_dev, const int8_t *p1_maps_dev, const int8_t *p2_maps_dev, void *stream);
+
+/* Start pools: games that start from GIVEN positions instead of sampled setups -- the reference's curriculum start states
+ * (curriculum_start_states_path, maenv:519-527; get_random_curriculum_init_fn, util.py:374-387), endgame training, evaluation from fixed
+ * test positions, search roots -- without leaving the batched path.  (Added without a struct or signature change: SGX_ABI_VERSION stays.)
+ *
+ * sgx_set_start_pool COPIES records [0, n_pool) of `pool` -- a handle of the same variant, board and device, typically one filled through
+ * sgx_import_state_checked or sgx_copy_envs -- into a buffer `h` owns (the pool handle may be destroyed or rewritten afterwards); pool =
+ * NULL clears it.  It waits for the device, and a previous buffer is freed only then.  While a pool is set, EVERY game start that would
+ * sample a setup -- sgx_reset with NULL maps (with or without env_select_dev) and every auto-reset of sgx_step, sgx_step_sync, sgx_step_n,
+ * sgx_rollout, sgx_step_ring and sgx_step_traj, also in the middle of a multi-step launch -- instead
+ *   1. draws j = rng_below(r, n_pool), r = the counter RNG's value for (seed, env_id_offset + env, game_no, stream STREAM_POOL = 4,
+ *      counter 0): a stream of its own, no other draw moves; game_no is the env's own counter, advanced exactly as without a pool;
+ *   2. loads record j whole: the four stored boards, the never-moved bitmaps, turn, max_turns, the recent-move pairs and the capture
+ *      events with their count; the env's game_no replaces the record's and the flags become the mover bit alone;
+ *   3. takes the record's mover as the first mover, or with SGX_POOL_RANDOM_FIRST_PLAYER (maenv:523) player -1 when
+ *      rng_below(r', 2) == 1 (r': the same stream, counter 1), else +1;
+ *   4. writes the mask, the observation, the sampled next action and player_dev of THAT position and mover.
+ * SGX_POOL_RESTART_CLOCK (util.py:382-383: turn = 0, max_turns = the handle's) is applied ONCE, to the private copy.
+ * Explicit maps passed to sgx_reset still win over the pool; with no pool set nothing changes anywhere, and clearing the pool restores
+ * that behaviour bit for bit.  While a pool is set, sampled setups need not be possible (the "more pieces than usable cells" refusal of
+ * sgx_reset / auto_reset applies only without one).  SGX_EINVAL, with nothing launched, for: a pool of another variant, board, record
+ * size or device; n_pool < 1 or larger than the pool handle; an unknown flag; a record whose game is over (the message names the first
+ * such index).  Not covered (SGX_EINVAL while a pool is set): auto_reset in launches with SGX_STEP_MASK_1D / _MASK_STATE_COORDS and in
+ * sgx_step_states.  sgx_start_pool_size: n_pool, 0 = none.
+ *
+ * sgx_set_start_index_out: int32 [N] (NULL = none) that every sgx_reset and every step of a handle WITH a pool (not: sgx_observe, sgx_expand,
+ * sgx_step_states and steps with SGX_STEP_MASK_1D / _MASK_STATE_COORDS, which run the ordinary kernels and leave it alone) writes the pool index of
+ * the env's CURRENT game into -- the game its new observation belongs to.  (A game that explicit maps started has no pool index: sgx_reset
+ * writes -1 for it, and its steps write the draw of its game number, which names no start.)  Addressed like
+ * sgx_step_io.done_dev: sgx_step_traj with results_per_slot writes step t's at start_index_dev[env + slot * slot_envs] (the buffer is
+ * then [n_slots][slot_envs]); at a slot with done = 1 the FINISHED game's index is the previous slot's.  The index is a function of
+ * (seed, env id, game number): a snapshot restored under the same pool reproduces it. */
+#define SGX_POOL_RANDOM_FIRST_PLAYER 1
+#define SGX_POOL_RESTART_CLOCK       2   /* turn = 0, max_turns = the handle's: util.py:382-383 */
+int sgx_set_start_pool(sgx_env *h, sgx_env *pool /* NULL = clear */, int64_t n_pool, int32_t flags);
+int sgx_set_start_index_out(sgx_env *h, int32_t *start_index_dev /* NULL = none */);
+int64_t sgx_start_pool_size(const sgx_env *h);   /* 0 = none */
 
 /* _get_current_obs (maenv:447-497) for every env's current mover, no state change.
  * obs_dev, fobs_dev, mask_dev and player_dev are laid out as in sgx_step_io; each is nullable.

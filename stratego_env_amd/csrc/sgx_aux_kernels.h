@@ -41,6 +41,39 @@ __global__ __launch_bounds__(64) void reset_kernel(const ResetParams P) {
                  make_int4(0, 0, 0, 0), 0, lane);
 }
 
+// sgx_reset of a handle with a start pool (no explicit maps): the selected envs' records become copies of pool record pool_index(env,
+// game number) -- whole, as 16-byte copies -- with the env's own game number (advanced like a sampled reset advances it) and the mover bit
+// alone as flags (the record's, or the draw of SGX_POOL_RANDOM_FIRST_PLAYER); start_index[env] receives the index.  One wave per env; the
+// record layout enters through sc_off only, so one kernel serves every board.
+__global__ __launch_bounds__(64) void reset_pool_kernel(const KParams P, const PoolParams PP, const uint8_t *__restrict__ select, const int sc_off) {
+    const int lane = threadIdx.x;
+    const int64_t env = blockIdx.x;
+    if (env >= P.n_envs) return;
+    if (select && select[env] == 0) return;
+    int4 *dst = reinterpret_cast<int4 *>(P.boards + env * (int64_t)P.rec_bytes);
+    const uint64_t g = (uint64_t)(P.env_id_offset + env);
+    const int game_no = __builtin_amdgcn_readfirstlane(dst[sc_off >> 4].w) + 1;
+    const int j = pool_index(P.seed, g, (uint64_t)game_no, PP.n_pool);               // < n_pool by construction (rng_below)
+    const int first = pool_first_player(P.seed, g, (uint64_t)game_no, PP.pool_flags);
+    const int4 *src = reinterpret_cast<const int4 *>(PP.pool + (int64_t)j * (int64_t)P.rec_bytes);
+    for (int i = lane; i < (P.rec_bytes >> 4); i += 64) {
+        int4 v = src[i];
+        if (i == (sc_off >> 4)) {                     // {turn, flags, max_turns, game_no}
+            const bool m1 = first ? first == -1 : (v.y & F_PLAYER_M1) != 0;
+            v.y = m1 ? F_PLAYER_M1 : 0;
+            v.w = game_no;
+        }
+        dst[i] = v;
+    }
+    if (lane == 0 && PP.start_index) PP.start_index[env] = j;
+}
+
+// sgx_reset with explicit maps on a handle with a start pool: the selected envs' games have no pool index
+__global__ void start_index_none_kernel(int32_t *__restrict__ start_index, const uint8_t *__restrict__ select, const int64_t n) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < n && (!select || select[i] != 0)) start_index[i] = -1;
+}
+
 // ---------------------------------------------------------------------------------------------
 // standalone sampler: k-th set byte of each env's mask (maenv:830-834 with the counter RNG)
 // ---------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 //   valid moves       impl:399-517                                         lane_gen_moves (bitboards, mover's perspective)
 //   endings           impl:1031-1043                                       lane_finish
 //   random setups     util.py:13-53 (counter RNG, sgx_layout.h)               lane_sample_boards
+//   start states      maenv:519-527, util.py:374-387 (a pool of positions)   lane_load_start
 #pragma once
 
 #ifndef SGX_HD
@@ -413,6 +414,26 @@ SGX_HD void lane_load(LaneGame &g, const uint8_t *rec) {
     g.turn = sc[0]; g.flags = sc[1]; g.max_turns = sc[2]; g.game_no = sc[3];
     g.n_events = sc[4] < (int)G::EVL_MAX ? sc[4] : (int)G::EVL_MAX;
     g.rp0 = sc[5]; g.rp1 = sc[6];
+}
+// A game that starts from a start pool (sgx_set_start_pool; load_start_record of sgx_step.h for one lane): the pool's record `j =
+// pool_index(...)` whole -- boards, never-moved bits, clock, recent-move pairs -- and its capture events copied into the game's own
+// list `ev` (entries beyond the record's count are cleared).  The env keeps its game number (g.game_no, already advanced); the flags
+// become the mover bit alone: the record's, or the draw of SGX_POOL_RANDOM_FIRST_PLAYER.  Returns j.
+template <class G>
+SGX_HD int lane_load_start(LaneGame &g, uint16_t *ev, const uint8_t *pool, int n_pool, int pool_flags, int rec_bytes, int max_events, uint64_t seed,
+                           uint64_t gid) {
+    const int game_no = g.game_no;
+    const int j = pool_index(seed, gid, (uint64_t)game_no, n_pool);
+    const uint8_t *rec = pool + (int64_t)j * rec_bytes;
+    lane_load<G>(g, rec);
+    g.game_no = game_no;
+    const int first = pool_first_player(seed, gid, (uint64_t)game_no, pool_flags);
+    const bool m1 = first ? first == -1 : (g.flags & F_PLAYER_M1) != 0;
+    g.flags = m1 ? F_PLAYER_M1 : 0;
+    const uint16_t *pev = reinterpret_cast<const uint16_t *>(rec + G::EVL_OFF);
+    for (int i = 0; i < G::EVL_MAX; ++i)
+        if (i < max_events) ev[i] = i < g.n_events ? pev[i] : (uint16_t)0;
+    return j;
 }
 template <class G>
 SGX_HD void lane_store(const LaneGame &g, uint8_t *rec) {

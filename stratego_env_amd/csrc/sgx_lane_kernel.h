@@ -193,13 +193,13 @@ __device__ __forceinline__ void lane_emit_obs(const uint8_t *rec_base, const int
     wave_sync<G>();
 }
 
-template <int R_, int C_, bool OBSERVE>
-__global__ __launch_bounds__(64) void lane_kernel(const KParams P) {
+// POOL: the instantiation of a handle with a start pool (sgx_set_start_pool; kernels of their own, like step_kernel_pool)
+template <int R_, int C_, bool OBSERVE, bool POOL>
+__device__ __forceinline__ void lane_body(const KParams &P, uint8_t *lane_rec, const PoolParams *pp = nullptr) {
     using G = Geo<R_, C_>;
     using LG = LaneGeo<G>;
     static_assert(lane_geometry<G>(), "lane kernel: boards of at most 16 cells, a multiple of 4");
     constexpr int RC = G::RC, K = G::K, NA = G::NA;
-    extern __shared__ __attribute__((aligned(16))) uint8_t lane_rec[];     // 64 record images, stride rec_bytes + 16
     __shared__ LaneLds<G> L;
     const int lane = threadIdx.x;
     const int64_t grp = group_of_block(P);
@@ -278,14 +278,24 @@ __global__ __launch_bounds__(64) void lane_kernel(const KParams P) {
     bool wrote_reset = false;
     if (mode == 0 && P.io.auto_reset && ended_now && act) {      // the finished env starts its next game now
         g.game_no += 1;
-        lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
-        g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
-        player = 1; qi = 0;
-        for (int i = 0; i < G::EVL_MAX; ++i)
-            if (i < P.max_events) ev[i] = 0;
-        nvalid = lane_gen_moves<G>(g, 0, obst_abs, false, V);
+        if constexpr (POOL) {
+            lane_load_start<G>(g, ev, reinterpret_cast<const uint8_t *>(pp->pool), pp->n_pool, pp->pool_flags, P.rec_bytes, P.max_events, P.seed,
+                               (uint64_t)(P.env_id_offset + env));
+            player = (g.flags & F_PLAYER_M1) ? -1 : 1; qi = player == 1 ? 0 : 1;
+            nvalid = lane_gen_moves<G>(g, qi, obst_abs, false, V);
+        } else {
+            lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
+            g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
+            player = 1; qi = 0;
+            for (int i = 0; i < G::EVL_MAX; ++i)
+                if (i < P.max_events) ev[i] = 0;
+            nvalid = lane_gen_moves<G>(g, 0, obst_abs, false, V);
+        }
         wrote_reset = true;
     }
+    if constexpr (POOL)      // the pool index of the env's current game (KParams::start_index)
+        if (mode == 0 && act && pp->start_index)
+            pp->start_index[env] = pool_index(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no, pp->n_pool);
     if (act && P.io.player_dev) P.io.player_dev[env] = (int8_t)player;
     const bool changed = act && (ap.applied || wrote_reset);
     if (changed) lane_store<G>(g, myrec);
@@ -328,6 +338,16 @@ __global__ __launch_bounds__(64) void lane_kernel(const KParams P) {
             wave_sync<G>();
         }
     }
+}
+template <int R_, int C_, bool OBSERVE>
+__global__ __launch_bounds__(64) void lane_kernel(const KParams P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lane_rec[];     // 64 record images, stride rec_bytes + 16
+    lane_body<R_, C_, OBSERVE, false>(P, lane_rec);
+}
+template <int R_, int C_>
+__global__ __launch_bounds__(64) void lane_kernel_pool(const KParams P, const PoolParams PP) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lane_rec[];
+    lane_body<R_, C_, false, true>(P, lane_rec, &PP);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -376,14 +396,13 @@ struct alignas(16) StepsLds {
     } em[KSTEP_EMITTERS];
 };
 
-template <int R_, int C_>
-__global__ __launch_bounds__(64 * (1 + KSTEP_EMITTERS), SGX_KSTEP_MIN_WAVES) void lane_steps_kernel(const StepsParams SP) {
+template <int R_, int C_, bool POOL>
+__device__ __forceinline__ void lane_steps_body(const StepsParams &SP, uint8_t *steps_rec, const PoolParams *pp = nullptr) {
     using G = Geo<R_, C_>;
     using LG = LaneGeo<G, KSTEP_SUB>;
     static_assert(lane_geometry<G>(), "lane kernels: boards of at most 16 cells, a multiple of 4");
     constexpr int RC = G::RC, K = G::K, NA = G::NA, NT = 64 * (1 + KSTEP_EMITTERS);
     const KParams &P = SP.k;
-    extern __shared__ __attribute__((aligned(16))) uint8_t steps_rec[];    // 2 x 64 record images, stride rec_bytes + 16
     __shared__ StepsLds<G> L;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t env0 = P.env_first + group_of_block(P) * 64;
@@ -464,13 +483,23 @@ __global__ __launch_bounds__(64 * (1 + KSTEP_EMITTERS), SGX_KSTEP_MIN_WAVES) voi
             }
             if (P.io.auto_reset && ended_now && act) {                     // the finished env starts its next game now
                 g.game_no += 1;
-                lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
-                g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
-                player = 1;
-                for (int i = 0; i < G::EVL_MAX; ++i)
-                    if (i < P.max_events) ev[i] = 0;
-                nvalid = lane_gen_moves<G>(g, 0, obst_abs, false, V);
+                if constexpr (POOL) {
+                    lane_load_start<G>(g, ev, reinterpret_cast<const uint8_t *>(pp->pool), pp->n_pool, pp->pool_flags, P.rec_bytes, P.max_events, P.seed,
+                                       (uint64_t)(P.env_id_offset + env));
+                    player = (g.flags & F_PLAYER_M1) ? -1 : 1;
+                    nvalid = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V);
+                } else {
+                    lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
+                    g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
+                    player = 1;
+                    for (int i = 0; i < G::EVL_MAX; ++i)
+                        if (i < P.max_events) ev[i] = 0;
+                    nvalid = lane_gen_moves<G>(g, 0, obst_abs, false, V);
+                }
             }
+            if constexpr (POOL)      // the pool index of the env's current game, in this step's slot
+                if (act && pp->start_index)
+                    pp->start_index[renv] = pool_index(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no, pp->n_pool);
             if (act && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
             lane_store<G>(g, myrec);                                       // (always: the emitters read this step's image)
             // mask rows (coalesced out by this wave) and the next action
@@ -518,6 +547,16 @@ __global__ __launch_bounds__(64 * (1 + KSTEP_EMITTERS), SGX_KSTEP_MIN_WAVES) voi
             }
         }
     }
+}
+template <int R_, int C_>
+__global__ __launch_bounds__(64 * (1 + KSTEP_EMITTERS), SGX_KSTEP_MIN_WAVES) void lane_steps_kernel(const StepsParams SP) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t steps_rec[];    // 2 x 64 record images, stride rec_bytes + 16
+    lane_steps_body<R_, C_, false>(SP, steps_rec);
+}
+template <int R_, int C_>
+__global__ __launch_bounds__(64 * (1 + KSTEP_EMITTERS), SGX_KSTEP_MIN_WAVES) void lane_steps_kernel_pool(const StepsParams SP, const PoolParams PP) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t steps_rec[];
+    lane_steps_body<R_, C_, true>(SP, steps_rec, &PP);
 }
 
 }  // namespace

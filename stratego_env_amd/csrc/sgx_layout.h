@@ -233,6 +233,16 @@ struct KParams {
 #endif
 };
 
+// sgx_set_start_pool: what the *_pool kernels take NEXT TO KParams (the argument block of every other kernel stays what it was).  A game
+// starts from record pool_index(...) of these n_pool records (the handle's own copy, read-only for every launch) instead of a sampled
+// setup (load_start_record); pool_flags: SGX_POOL_RANDOM_FIRST_PLAYER.  start_index (sgx_set_start_index_out, NULL = none): the pool
+// index of every env's current game, addressed like io.done_dev.
+struct PoolParams {
+    const int8_t *pool;
+    int32_t n_pool, pool_flags;
+    int32_t *start_index;
+};
+
 #ifdef SGX_STAMPS
 #define STAMP(i)                                                                                   \
     do {                                                                                           \
@@ -281,7 +291,16 @@ __host__ __device__ inline uint64_t sgx_rng(uint64_t seed, uint64_t g, uint64_t 
     return sm_fin(h ^ (j * 0xD1B54A32D192ED03ull + ctr * 0x8CB92BA72F3D8DD7ull + 0x2545F4914F6CDD1Dull));
 }
 __host__ __device__ inline uint32_t rng_below(uint64_t r, uint32_t n) { return (uint32_t)(((r >> 32) * (uint64_t)n) >> 32); }
-enum { STREAM_SETUP = 0, STREAM_ACTION = 1, STREAM_SHUFFLE_P1 = 2, STREAM_SHUFFLE_P2 = 3 };
+enum { STREAM_SETUP = 0, STREAM_ACTION = 1, STREAM_SHUFFLE_P1 = 2, STREAM_SHUFFLE_P2 = 3, STREAM_POOL = 4 };
+// A game that starts from a start pool (sgx_set_start_pool): game `j` of env `g` takes record pool_index() and, with
+// SGX_POOL_RANDOM_FIRST_PLAYER, the first mover pool_first_player() says (0: the record's own).  A stream of its own: no other draw moves.
+__host__ __device__ inline int pool_index(uint64_t seed, uint64_t g, uint64_t j, int n_pool) {
+    return (int)rng_below(sgx_rng(seed, g, j, STREAM_POOL, 0), (uint32_t)n_pool);
+}
+__host__ __device__ inline int pool_first_player(uint64_t seed, uint64_t g, uint64_t j, int pool_flags) {
+    if (!(pool_flags & SGX_POOL_RANDOM_FIRST_PLAYER)) return 0;
+    return rng_below(sgx_rng(seed, g, j, STREAM_POOL, 1), 2u) == 1u ? -1 : 1;            // maenv:523
+}
 
 // ---------------------------------------------------------------------------------------------
 // small device helpers

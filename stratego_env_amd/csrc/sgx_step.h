@@ -110,6 +110,101 @@ struct GameInput {
     int a_raw;
     const int4 *src;      // WIDE boards (a record of more than two int4 per lane): staged straight from here in env_step
 };
+// The staging of a record as three functions: what env_step's prologue does, for load_start_record (a game that starts from a start pool).
+// load_game_from and the prologue keep their own inline text of the three: as calls of these functions
+// they cost two states_kernel instantiations at 10x10 a register and 68 bytes of scratch (profiles/start_pool_kernel_notes.txt has the
+// rule: no kernel of a handle without a pool may pay for the pool).
+// load_record: the global reads -- the whole record as one or two int4 per lane (issued by the prologue's caller BEFORE the workgroup
+// stages its tables, so that the two round trips overlap; WIDE boards read in stage_record's loop instead).
+template <class G, class KP>
+__device__ __forceinline__ void load_record(const KP &P, const int4 *src, const int lane, int4 &rq0, int4 &rq1) {
+    constexpr int Q_BOARDS = G::ST_OFF / 16, Q_REC = Q_BOARDS + G::TAIL_BYTES / 16, NLOAD = (Q_REC + G::LPG - 1) / G::LPG;
+    const int nq = G::BIG ? Q_REC : min(P.rec_bytes >> 4, Q_REC);
+    if constexpr (NLOAD <= 2) {
+        if (lane < nq) rq0 = src[lane];
+        if constexpr (NLOAD > 1)
+            if (lane + G::LPG < nq) rq1 = src[lane + G::LPG];
+    }
+}
+// stage_record: the split of the record into the four stored boards (L.b) and the image from ST_OFF on (L.tail: bitmaps, scalars, events).
+template <class G, int NB, class KP>
+__device__ __forceinline__ void stage_record(Lds<G, NB> &L, const KP &P, const int4 rq0, const int4 rq1, const int4 *src, const int lane) {
+    constexpr int Q_BOARDS = G::ST_OFF / 16, Q_REC = Q_BOARDS + G::TAIL_BYTES / 16, NLOAD = (Q_REC + G::LPG - 1) / G::LPG;
+    int4 *dst = reinterpret_cast<int4 *>(&L.b[0][0]);
+    int4 *tl = reinterpret_cast<int4 *>(L.tail);
+    if constexpr (NLOAD <= 2) {
+        if (lane < Q_BOARDS) dst[lane] = rq0;
+        else if (lane < Q_REC) tl[lane - Q_BOARDS] = rq0;
+        if constexpr (NLOAD > 1) {
+            if (lane + G::LPG < Q_BOARDS) dst[lane + G::LPG] = rq1;
+            else if (lane + G::LPG < Q_REC) tl[lane + G::LPG - Q_BOARDS] = rq1;
+        }
+    } else {                                              // WIDE boards: the record is several KiB, staged in a loop
+        const int nq = G::BIG ? Q_REC : min(P.rec_bytes >> 4, Q_REC);
+        for (int i = lane; i < Q_REC; i += G::LPG) {
+            const int4 v = i < nq ? src[i] : make_int4(0, 0, 0, 0);
+            if (i < Q_BOARDS) dst[i] = v;
+            else tl[i - Q_BOARDS] = v;
+        }
+    }
+}
+// rebuild_derived: the boards the record keeps sparsely -- never-moved bitmaps -> byte boards, recent-move pairs -> the (cleared)
+// recent-move boards (capture events stay a list)
+template <class G, int NB>
+__device__ __forceinline__ void rebuild_derived(Lds<G, NB> &L, const int rp0, const int rp1, const int lane) {
+    constexpr int RC = G::RC, S = G::S;
+    const uint32_t *stb = reinterpret_cast<const uint32_t *>(L.tail);
+#pragma unroll
+    for (int cc = 0; cc < G::CPL; ++cc) {
+        const int i = lane + G::LPG * cc;
+        if (i < RC) {
+            L.b[B_STILL][i] = (int8_t)((stb[i >> 5] >> (i & 31)) & 1u);
+            L.b[B_STILL + 1][i] = (int8_t)((stb[G::SB / 4 + (i >> 5)] >> (i & 31)) & 1u);
+        }
+    }
+    if constexpr (G::BIG) {                      // general-state image: the recent-move boards are dense
+        for (int i = lane; i < S; i += G::LPG) {
+            L.b[B_RECENT][i] = (int8_t)L.tail[G::RECB_OFF - G::ST_OFF + i];
+            L.b[B_RECENT + 1][i] = (int8_t)L.tail[G::RECB_OFF - G::ST_OFF + G::S_PAD + i];
+        }
+    } else if (lane < 4) {
+        const int pr = (((lane >> 1) ? rp1 : rp0) >> (16 * (lane & 1))) & 0xFFFF;
+        if (pr >> G::CELL_BITS) L.b[B_RECENT + (lane >> 1)][G::pair_cell(pr)] = (int8_t)G::pair_code(pr);
+    }
+}
+
+// A game that starts from the handle's start pool (sgx_set_start_pool) instead of a sampled setup: record pool_index() of the pool is
+// staged WHOLE over the game's LDS boards and record image -- the four stored boards, the never-moved bitmaps, turn and max_turns, the
+// recent-move pairs, the capture events and their count -- like the prologue stages the env's own record.  The env keeps its game number;
+// the flags of the new game are the mover bit alone.  Returns what the caller holds in registers.
+struct StartScalars {
+    int turn, max_turns, n_events, rp0, rp1, player;
+};
+template <class G, int NB, class KP, class PPT>
+__device__ __forceinline__ StartScalars load_start_record(Lds<G, NB> &L, const KP &P, const PPT &PP, const int64_t env, const int game_no, const int lane) {
+    const uint64_t g = (uint64_t)(P.env_id_offset + env);
+    const int j = pool_index(P.seed, g, (uint64_t)game_no, PP.n_pool);           // < n_pool by construction (rng_below)
+    const int4 *src = reinterpret_cast<const int4 *>(PP.pool + (int64_t)j * (int64_t)P.rec_bytes);
+    int4 rq0 = make_int4(0, 0, 0, 0), rq1 = rq0;
+    load_record<G>(P, src, lane, rq0, rq1);
+    for (int i = lane; i < G::S / 4; i += G::LPG) {
+        reinterpret_cast<int *>(L.b[B_RECENT])[i] = 0;
+        reinterpret_cast<int *>(L.b[B_RECENT + 1])[i] = 0;
+    }
+    stage_record(L, P, rq0, rq1, src, lane);
+    wave_sync<G>();
+    const int4 sc = reinterpret_cast<const int4 *>(L.tail + 2 * G::SB)[0], sc2 = reinterpret_cast<const int4 *>(L.tail + 2 * G::SB)[1];
+    StartScalars st;
+    st.turn = uni<G>(sc.x); st.max_turns = uni<G>(sc.z);
+    st.n_events = min(uni<G>(sc2.x), (int)G::EVL_MAX);
+    st.rp0 = uni<G>(sc2.y); st.rp1 = uni<G>(sc2.z);
+    const int first = pool_first_player(P.seed, g, (uint64_t)game_no, PP.pool_flags);
+    st.player = first ? first : ((uni<G>(sc.y) & F_PLAYER_M1) ? -1 : 1);
+    rebuild_derived(L, st.rp0, st.rp1, lane);
+    wave_sync<G>();
+    return st;
+}
+
 // (src: the game's record -- global memory, or the LDS image of sgx_step_states' fused kernel)
 template <class G, class KP>
 __device__ __forceinline__ GameInput load_game_from(const KP &P, const int4 *src, const int64_t env, const int lane) {
@@ -118,7 +213,7 @@ __device__ __forceinline__ GameInput load_game_from(const KP &P, const int4 *src
     const int4 zero4 = make_int4(0, 0, 0, 0);
     GameInput in{zero4, zero4, zero4, 0, src};
     const int nq = G::BIG ? Q_REC : min(P.rec_bytes >> 4, Q_REC);
-    if constexpr (NLOAD <= 2) {
+    if constexpr (NLOAD <= 2) {                                  // (TWIN: load_record)
         if (lane < nq) in.rq0 = src[lane];
         if constexpr (NLOAD > 1)
             if (lane + G::LPG < nq) in.rq1 = src[lane + G::LPG];
@@ -163,6 +258,11 @@ struct StepCarry {
     uint8_t *mask;
     int slot;                 // ... and the slot number (per-slot results and the action log of sgx_step_traj: KParams::traj_*)
 };
+// the carry of steps_kernel_pool's one copy of the step (PERSIST_ = 3): whether this is the launch's first step is a run-time flag there
+// (a struct of its own: StepCarry keeps its size, part of it lives in scratch memory in some instantiations of steps_kernel)
+struct StepCarryPool : StepCarry {
+    bool first;
+};
 
 // One game's env.step() by one wave (called with the wave's private LDS region).
 // `shared` = the workgroup's tables (shared_table_bytes): templates + code table, or LUTs + quad tables
@@ -171,11 +271,23 @@ struct StepCarry {
 // PERSIST_ (steps_kernel): the call is one of several consecutive steps of the same game by the same wave.  Only the FIRST stages the record;
 // later ones find the boards -- dense, never-moved bytes, recent-move codes, the event list -- where the step before left them in LDS,
 // take the scalars and the action from *carry, and only the LAST writes the record back (if any step changed it).
-template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, class KP = KParams>
+// POOL: the instantiation the host launches while the handle has a start pool (sgx_set_start_pool): an auto-reset loads a pool record
+// (load_start_record) instead of sampling boards, and every step writes the pool index of the env's current game (KParams::start_index).
+// A template parameter, not a run-time branch: the kernels of a handle without a pool stay exactly what they were.
+// whether a step is its launch's first: a compile-time constant for PERSIST_ 0 / 1 / 2, the carry's flag for 3
+template <int PERSIST_>
+__device__ __forceinline__ auto first_of(const StepCarry *carry) {
+    if constexpr (PERSIST_ == 3) return static_cast<const StepCarryPool *>(carry)->first;
+    else return std::integral_constant<bool, PERSIST_ != 2>{};
+}
+template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, bool POOL = false, class KP = KParams, class PPT = PoolParams>
 __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsKind<KIND>::NIB_CH> &L, const uint8_t *shared, const uint8_t *obst_s,
                                          const int64_t env, const int lane, const GameInput &in, int8_t *rec_out = nullptr, StepOut *so = nullptr,
-                                         StepCarry *carry = nullptr, const bool last = true) {
-    constexpr bool PERSIST = PERSIST_ != 0, first = PERSIST_ != 2;      // PERSIST_: 0 = a launch of its own, 1 = the first step of a multi-step launch, 2 = a later one
+                                         StepCarry *carry = nullptr, const bool last = true, const PPT *pp = nullptr) {
+    // PERSIST_: 0 = a launch of its own, 1 = the first step of a multi-step launch, 2 = a later one, 3 = any step of one (carry->first tells: the
+    // one copy of the step that steps_kernel_pool holds)
+    constexpr bool PERSIST = PERSIST_ != 0;
+    const auto first = first_of<PERSIST_>(carry);
     using G = Geo<R_, C_, VAR>;
     using PS = typename ObsKind<KIND>::P;
     using FS = typename ObsKind<KIND>::F;
@@ -513,11 +625,26 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     bool wrote_reset = false;
     if (P.mode == 0 && ended_now && P.io.auto_reset) {
         game_no += 1;
-        sample_boards(L, P, (uint64_t)(P.env_id_offset + env), (uint64_t)game_no, lane);
-        turn = 0; flags = 0; player = 1; qi = 0; over = false;
-        n_events = 0; rp0 = rp1 = 0;
-        nvalid = want_bits ? gen_mask(L, 0, false, lane) : 1;          // (without mask and sampler nobody looks at the count of a fresh game)
+        if constexpr (POOL) {                  // a position of the start pool, with its own clock, mover, recent moves and captures
+            const StartScalars st = load_start_record(L, P, *pp, env, game_no, lane);
+            turn = st.turn; max_turns = st.max_turns; n_events = st.n_events; rp0 = st.rp0; rp1 = st.rp1;
+            player = st.player; qi = player == 1 ? 0 : 1; over = false;
+            flags = player == -1 ? F_PLAYER_M1 : 0;
+        } else {
+            sample_boards(L, P, (uint64_t)(P.env_id_offset + env), (uint64_t)game_no, lane);
+            turn = 0; flags = 0; player = 1; qi = 0; over = false;
+            n_events = 0; rp0 = rp1 = 0;
+        }
+        nvalid = want_bits ? gen_mask(L, qi, false, lane) : 1;         // (without mask and sampler nobody looks at the count of a fresh game)
         wrote_reset = true;
+    }
+    if constexpr (POOL) {
+        // the pool index of the env's CURRENT game (the one the outputs below belong to): a function of the env and its game number, so
+        // nothing is carried
+        if (P.mode == 0 && pp->start_index) {
+            const int j = pool_index(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)game_no, pp->n_pool);
+            if (lane == 0) pp->start_index[renv] = j;
+        }
     }
 
     STAMP(4);   // results / terminal handling done
@@ -703,6 +830,90 @@ constexpr int steps_waves_per_simd() {
     constexpr int w = waves_per_simd<G, KIND, false>();
     return (G::RC <= 64 && G::RC % 4 != 0 && !ObsKind<KIND>::NOOBS && w > 6) ? 6 : w;
 }
+// the argument block of steps_kernel_pool: steps_kernel's, then the pool
+struct WaveStepsParamsPool {
+    WaveStepsParams w;
+    PoolParams pool;
+};
+__device__ __forceinline__ const SGX_KERNARG WaveStepsParams *wsp_of(const SGX_KERNARG WaveStepsParams *p) { return p; }
+__device__ __forceinline__ const SGX_KERNARG WaveStepsParams *wsp_of(const SGX_KERNARG WaveStepsParamsPool *p) { return &p->w; }
+// the body of steps_kernel_pool (TWIN: steps_kernel below, whose table staging this restates)
+template <int R_, int C_, int KIND, int VAR, class SPT = WaveStepsParamsPool>
+__device__ __forceinline__ void steps_body(const SPT &SP) {
+    constexpr bool POOL = true;
+    using G = Geo<R_, C_, VAR>;
+    static_assert(VAR == 0 || (VAR == 2 && ObsKind<KIND>::NOOBS), "two games per wave: the no-observation kinds only");
+    using PS = typename ObsKind<KIND>::P;
+    using FS = typename ObsKind<KIND>::F;
+    constexpr bool FULL = ObsKind<KIND>::FULL, ORIG = ObsKind<KIND>::ORIG;
+    // The parameters are read through the kernel-argument segment's address IN ITS OWN ADDRESS SPACE (SGX_KERNARG, sgx_layout.h), and the loop
+    // below hides that address from the optimiser once per step: otherwise every field env_step looks at is hoisted out of the loop and held
+    // in scalar registers for its whole length (106 of 106 SGPRs, 324 bytes of scratch); re-read per step they cost a few scalar loads from
+    // the constant cache.  (Through a generic pointer -- the first version of this kernel -- the re-reads were 17 VECTOR loads per game and
+    // step, each followed by a wait for everything the wave had in flight, its observation stores included: 5x5 95 -> 76 us per step, 15x15
+    // 369 -> 311, 6x6 111 -> 99, 10x10 246 -> 241 on one set of buffers, tools/lib_ab.py.)
+#if defined(__HIP_DEVICE_COMPILE__)
+    const SGX_KERNARG SPT *top = (const SGX_KERNARG SPT *)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    const SPT *top = &SP;                         // (host pass of the single-source compile: never executed)
+#endif
+    const SGX_KERNARG WaveStepsParams *spp = wsp_of(top);
+    const SGX_KERNARG KParams &P = spp->k;
+    __shared__ Lds<G, ObsKind<KIND>::NIB_CH> LW[G::WPB * G::GPW];
+    __shared__ alignas(16) uint8_t shared[shared_table_bytes<G, KIND>()];
+    __shared__ alignas(16) uint8_t obst_s[G::OBST_BYTES + COMBAT_BYTES];
+    const int lane = threadIdx.x & (G::LPG - 1), slot = threadIdx.x / G::LPG;
+    const int64_t env = P.env_first + group_of_block(P) * (G::WPB * G::GPW) + slot;
+    const GameInput in = load_game<G, false>(P, env, lane);
+    const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
+    if constexpr (ObsKind<KIND>::NOOBS) {
+    } else if constexpr (ORIG) {
+        float *lut_s = reinterpret_cast<float *>(shared);
+        const f32x4 *lsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0)]);
+        for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s)[i] = lsrc[i];
+        build_quad_table<G, PS>(reinterpret_cast<uint32_t *>(lut_s + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
+        if constexpr (FULL) {
+            const f32x4 *fsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0) + 1]);
+            for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s + OBS_TAB_DWORDS)[i] = fsrc[i];
+            build_quad_table<G, FS>(reinterpret_cast<uint32_t *>(lut_s + OBS_TAB_DWORDS + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
+        }
+    } else {
+        constexpr int NP = tmpl_lds_bytes<G, KIND>(false), NF = FULL ? tmpl_lds_bytes<G, KIND>(true) : 0;
+        const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
+        for (int i = threadIdx.x; i < NP / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared)[i] = tp[i];
+        if constexpr (FULL) {
+            const int4 *tf = reinterpret_cast<const int4 *>(P.tab->tmpl[(raw ? 2 : 0) + 1]);
+            for (int i = threadIdx.x; i < NF / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP)[i] = tf[i];
+        }
+        const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
+        for (int i = threadIdx.x; i < CODETAB_BYTES / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP + NF)[i] = ct[i];
+    }
+    for (int i = threadIdx.x; i < G::S / 4; i += 64 * G::WPB) reinterpret_cast<int *>(obst_s)[i] = reinterpret_cast<const int *>(P.tab->obstacles)[i];
+    for (int i = threadIdx.x; i < COMBAT_BYTES / 4; i += 64 * G::WPB)
+        reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
+    __syncthreads();   // from here on every wave works on its own game, for all n_steps
+    if (env >= P.n_envs) return;
+    int set = spp->first_set;
+    const int n_steps = spp->n_steps;
+    if constexpr (POOL) {
+        StepCarryPool carry{};
+        // a handle with a start pool: ONE copy of the step (env_step<PERSIST_ = 3, POOL>) plays the first step and the later ones -- and, with
+        // n_steps = 1, the launches of sgx_step / sgx_rollout's chains: the pool costs one instantiation per observation kind
+        for (int t = 0; t < n_steps; ++t) {
+            const SGX_KERNARG SPT *tp = top;
+            int lane_t = lane, slot_t = slot;
+            asm volatile("" : "+s"(tp), "+v"(lane_t), "+v"(slot_t));
+            const SGX_KERNARG WaveStepsParams *sp = wsp_of(tp);
+            if (t && sp->barrier) __builtin_amdgcn_s_barrier();
+            steps_outputs_of(sp, set, carry);
+            carry.first = t == 0;
+            env_step<R_, C_, KIND, false, false, VAR, 3, true>(sp->k, LW[slot_t], shared, obst_s, env, lane_t, in, nullptr, nullptr, &carry, t == n_steps - 1, &tp->pool);
+            set = set + 1 == sp->n_sets ? 0 : set + 1;
+        }
+    }
+}
+// (steps_kernel is its own text, not a call of steps_body: as a call three of its instantiations paid a VGPR or 8 bytes of scratch.
+//  TWIN: steps_body below restates the table staging for steps_kernel_pool.)
 template <int R_, int C_, int KIND, int VAR = 0>
 __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd<Geo<R_, C_, VAR>, KIND>())) void steps_kernel(const WaveStepsParams SP) {
     using G = Geo<R_, C_, VAR>;
@@ -780,6 +991,12 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
         set = set + 1 == sp->n_sets ? 0 : set + 1;
     }
 }
+// the launches of a handle with a start pool, single steps and multi-step alike (the carry takes the scalars of the pool record a restart
+// loaded); also the 'original' channel kinds, which have no steps_kernel
+template <int R_, int C_, int KIND, int VAR = 0>
+__global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd<Geo<R_, C_, VAR>, KIND>())) void steps_kernel_pool(const WaveStepsParamsPool SP) {
+    steps_body<R_, C_, KIND, VAR>(SP);
+}
 
 // sgx_step_sync on a handful of games (the N = 1 facade, config 1): latency, not throughput.  ONE game per 512-thread workgroup: wave 0
 // plays the step (env_step<SPLIT>), then all eight waves emit the mask and the observations -- 30 KiB by one wave is 4.3 of the step's
@@ -787,9 +1004,9 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
 // the caller does not wait for the end-of-kernel processing of the queue (signal, cache write-back, wake-up: ~5 us).
 // 'extended' kinds on 4-aligned one-game-per-wave boards.
 constexpr int SINGLE_WAVES = 8;
-template <int R_, int C_, int KIND>
-__global__ __launch_bounds__(64 * SINGLE_WAVES) void single_kernel(const KParams P, uint32_t *__restrict__ done_count, uint32_t *__restrict__ flag_host,
-                                                                 const uint32_t seq) {
+template <int R_, int C_, int KIND, bool POOL>
+__device__ __forceinline__ void single_body(const KParams &P, uint32_t *__restrict__ done_count, uint32_t *__restrict__ flag_host, const uint32_t seq,
+                                            const PoolParams *pp = nullptr) {
     using G = Geo<R_, C_>;
     using PS = typename ObsKind<KIND>::P;
     using FS = typename ObsKind<KIND>::F;
@@ -819,7 +1036,7 @@ __global__ __launch_bounds__(64 * SINGLE_WAVES) void single_kernel(const KParams
         for (int i = tid; i < COMBAT_BYTES / 4; i += NT) reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
     }
     __syncthreads();
-    if (wave == 0) env_step<R_, C_, KIND, false, true>(P, L, shared, obst_s, env, lane, in, nullptr, &so);
+    if (wave == 0) env_step<R_, C_, KIND, false, true, 0, 0, POOL>(P, L, shared, obst_s, env, lane, in, nullptr, &so, nullptr, true, pp);
     __syncthreads();
     if (P.io.mask_dev) emit_mask<G, NT>(L, P.io.mask_dev + env * (int64_t)G::NA, tid);
     const uint8_t *codetab = shared + NP + NF;
@@ -853,6 +1070,16 @@ __global__ __launch_bounds__(64 * SINGLE_WAVES) void single_kernel(const KParams
         }
         if (last) __hip_atomic_store(flag_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+template <int R_, int C_, int KIND>
+__global__ __launch_bounds__(64 * SINGLE_WAVES) void single_kernel(const KParams P, uint32_t *__restrict__ done_count, uint32_t *__restrict__ flag_host,
+                                                                 const uint32_t seq) {
+    single_body<R_, C_, KIND, false>(P, done_count, flag_host, seq);
+}
+template <int R_, int C_, int KIND>
+__global__ __launch_bounds__(64 * SINGLE_WAVES) void single_kernel_pool(const KParams P, const PoolParams PP, uint32_t *__restrict__ done_count,
+                                                                      uint32_t *__restrict__ flag_host, const uint32_t seq) {
+    single_body<R_, C_, KIND, true>(P, done_count, flag_host, seq, &PP);
 }
 
 }  // namespace

@@ -125,6 +125,7 @@ struct sgx_env {
     int general_states;          // sgx_set_general_states: 0 = flagged states stay sanitised, otherwise the second, general-state pass redoes them
     int no_multi_step;           // SGX_MULTI_STEP=0 (or a runtime that refuses the LDS size): sgx_step_n / sgx_step_ring never take lane_steps_kernel
     int multi_step_attr;         // lane_steps_kernel's dynamic-LDS attribute has been raised
+    int multi_step_attr_pool;    // ... and lane_steps_kernel_pool's
     int last_kind;               // sgx_last_launch_kind: which kernel the last step / observe launch of this handle was
     int multi_step_wave;         // SGX_MULTI_STEP_WAVE: the multi-step launch of the wave-per-game kernels (steps_kernel) too
     int steps_barrier;           // sgx_set_steps_barrier / SGX_STEPS_BARRIER: -1 auto (long rings that render float32 observations: steps_kernel), 0 never, 1 always
@@ -135,6 +136,12 @@ struct sgx_env {
     int ring_tab_cap, ring_tab_n;
     hipEvent_t ring_tab_ev;
     hipStream_t ring_tab_stream;
+    // sgx_set_start_pool: the handle's OWN copy of the pool's records (NULL = none: games start from sampled setups), their number and the
+    // SGX_POOL_* flags the kernels look at; sgx_set_start_index_out: where the launches write the pool index of every env's current game
+    int8_t *pool;
+    int64_t n_pool;
+    int pool_flags;
+    int32_t *start_index;
 };
 
 namespace {
@@ -213,6 +220,16 @@ KParams make_params(const sgx_env *h) {
     return p;
 }
 
+// what the *_pool kernels take next to KParams; start_index moved on by `index_off` entries (a step of an sgx_step_traj call as a launch of its own)
+PoolParams make_pool_params(const sgx_env *h, int64_t index_off = 0) {
+    PoolParams pp;
+    pp.pool = h->pool;
+    pp.n_pool = (int32_t)h->n_pool;
+    pp.pool_flags = h->pool_flags;
+    pp.start_index = (h->pool && h->start_index) ? h->start_index + index_off : nullptr;
+    return pp;
+}
+
 int check_cfg(const sgx_config *cfg) {
     if (!cfg) return fail(SGX_EINVAL, "cfg is NULL%s");
     if (cfg->rows < 3 || cfg->cols < 3) return fail(SGX_EINVAL, "Both rows and columns have to be at least 3%s");
@@ -233,7 +250,7 @@ int check_cfg(const sgx_config *cfg) {
 
 // sampled setups without a table place piece_counts pieces on the usable back rows: they have to fit
 static int check_random_setups(const sgx_env *h) {
-    if (h->setups) return SGX_OK;
+    if (h->setups || h->pool) return SGX_OK;          // (a start pool: no game start samples a setup)
     int total = 0;
     for (int i = 0; i < 12; ++i) total += h->cfg.piece_counts[i];
     if (total > h->cfg.usable_rows * h->cfg.cols) return fail(SGX_EINVAL, "random setups: more pieces than usable cells%s");
@@ -482,6 +499,7 @@ SGX_API int sgx_destroy(sgx_env *h) {
     if (h->boards) (void)hipFree(h->boards);
     if (h->tab) (void)hipFree(h->tab);
     if (h->setups) (void)hipFree(h->setups);
+    if (h->pool) (void)hipFree(h->pool);
     if (h->stamps) (void)hipFree(h->stamps);
     for (int c = 0; c < SGX_MAX_CHAINS; ++c) {
         if (h->chain_stream[c]) (void)hipStreamDestroy(h->chain_stream[c]);
@@ -582,12 +600,84 @@ SGX_API int sgx_set_setup_table(sgx_env *h, const uint8_t *table_host, int64_t n
     return SGX_OK;
 }
 
+namespace { int same_variant(const sgx_env *a, const sgx_env *b); }
+static int check_aligned(const char *fn, const char *name, const void *ptr, int align);
+
+SGX_API int sgx_set_start_pool(sgx_env *h, sgx_env *pool, int64_t n_pool, int32_t flags) {
+    if (!h) return fail(SGX_EINVAL, "sgx_set_start_pool: handle is NULL%s");
+    if (!pool) {                                             // clear: games start from sampled setups again
+        if (!h->pool) return SGX_OK;
+        SGX_ON_DEVICE(h->device);
+        HIP_TRY(hipDeviceSynchronize());                     // (no launch that reads the buffer is in flight when it goes)
+        HIP_TRY(hipFree(h->pool));
+        h->pool = nullptr; h->n_pool = 0; h->pool_flags = 0;
+        return SGX_OK;
+    }
+    if (flags & ~(SGX_POOL_RANDOM_FIRST_PLAYER | SGX_POOL_RESTART_CLOCK)) return fail(SGX_EINVAL, "sgx_set_start_pool: unknown flag%s");
+    if (pool->cfg.rows != h->cfg.rows || pool->cfg.cols != h->cfg.cols) return fail(SGX_EINVAL, "sgx_set_start_pool: the pool was created for another board size%s");
+    if (int rc = same_variant(h, pool)) return rc;
+    if (n_pool < 1 || n_pool > pool->n_envs || n_pool > 0x7fffffff) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "sgx_set_start_pool: n_pool = %lld, the pool handle holds %lld records", (long long)n_pool, (long long)pool->n_envs);
+        return fail(SGX_EINVAL, "%s", buf);
+    }
+    SGX_ON_DEVICE(h->device);
+    HIP_TRY(hipDeviceSynchronize());                         // the pool's records are complete; nothing reads the previous buffer any more
+    // the records' scalars on the host: no finished game may be a start state, and SGX_POOL_RESTART_CLOCK is applied here, once
+    std::vector<int32_t> sc((size_t)n_pool * 8);
+    HIP_TRY(hipMemcpy2D(sc.data(), 32, pool->boards + pool->sc_off, (size_t)pool->rec_bytes, 32, (size_t)n_pool, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n_pool; ++i)
+        if (sc[8 * i + 1] & F_OVER) {
+            char buf[160];
+            snprintf(buf, sizeof(buf), "sgx_set_start_pool: the game of pool record %lld is over (a start state must have a next move)", (long long)i);
+            return fail(SGX_EINVAL, "%s", buf);
+        }
+    int8_t *buf_dev = nullptr;
+    const size_t bytes = (size_t)n_pool * h->rec_bytes;
+    if (hipMalloc((void **)&buf_dev, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(SGX_ENOMEM, "sgx_set_start_pool: device allocation failed%s"); }
+    hipError_t e = hipMemcpy(buf_dev, pool->boards, bytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess && (flags & SGX_POOL_RESTART_CLOCK)) {                   // util.py:382-383: turn 0, the handle's max_turns
+        for (int64_t i = 0; i < n_pool; ++i) { sc[8 * i] = 0; sc[8 * i + 2] = h->cfg.max_turns; }
+        e = hipMemcpy2D(buf_dev + h->sc_off, (size_t)h->rec_bytes, sc.data(), 32, 32, (size_t)n_pool, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { (void)hipFree(buf_dev); return fail(SGX_EDEVICE, "sgx_set_start_pool: %s", hipGetErrorString(e)); }
+    if (h->pool) (void)hipFree(h->pool);                     // (the device is idle: see above)
+    h->pool = buf_dev;
+    h->n_pool = n_pool;
+    h->pool_flags = flags & SGX_POOL_RANDOM_FIRST_PLAYER;
+    return SGX_OK;
+}
+
+SGX_API int sgx_set_start_index_out(sgx_env *h, int32_t *start_index_dev) {
+    if (!h) return fail(SGX_EINVAL, "sgx_set_start_index_out: handle is NULL%s");
+    if (int rc = check_aligned("sgx_set_start_index_out", "start_index_dev", start_index_dev, 4)) return rc;
+    h->start_index = start_index_dev;
+    return SGX_OK;
+}
+
+SGX_API int64_t sgx_start_pool_size(const sgx_env *h) { return (h && h->pool) ? h->n_pool : 0; }
+
 SGX_API int sgx_reset(sgx_env *h, const uint8_t *env_select_dev, const int8_t *p1_maps_dev, const int8_t *p2_maps_dev, void *stream) {
     if (!h) return fail(SGX_EINVAL, "handle is NULL%s");
     if ((p1_maps_dev == nullptr) != (p2_maps_dev == nullptr)) return fail(SGX_EINVAL, "pass both piece maps or neither%s");
     if (!p1_maps_dev)
         if (int rc = check_random_setups(h)) return rc;
     SGX_ON_DEVICE(h->device);
+    if (h->pool) {
+        const KParams p = make_params(h);
+        const PoolParams pp = make_pool_params(h);
+        const unsigned grid = (unsigned)h->n_envs;
+        if (!p1_maps_dev) {         // every selected env starts from a record of the start pool
+            reset_pool_kernel<<<grid, 64, 0, (hipStream_t)stream>>>(p, pp, env_select_dev, h->sc_off);
+            HIP_TRY(hipGetLastError());
+            return SGX_OK;
+        }
+        if (pp.start_index) {       // explicit maps win over the pool: such a game has no pool index
+            start_index_none_kernel<<<(grid + 255) / 256, 256, 0, (hipStream_t)stream>>>(pp.start_index, env_select_dev, h->n_envs);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     ResetParams rp;
     rp.k = make_params(h);
     rp.select = env_select_dev;
@@ -728,7 +818,7 @@ struct OutSets {
     int64_t obs_b, fobs_b, mask_b;
 };
 
-static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_sets = 1);
+static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_sets = 1, int64_t start_index_off = 0, bool allow_pool = true);
 
 // ONE step of a rollout call as a launch of its own, writing output set / slot `set`: what the multi-step launches fall back to (calls
 // they do not cover, the odd step a chunk leaves over).
@@ -751,7 +841,7 @@ static int launch_set_step(sgx_env *h, const KParams &p_in, const OutSets &sets,
     io.invalid_action_dev = at(io.invalid_action_dev, r);
     io.ending_invalid_dev = at(io.ending_invalid_dev, r);
     p1.io = io;
-    if (int rc = launch_step(h, p1, stream, sets.n_sets)) return rc;
+    if (int rc = launch_step(h, p1, stream, sets.n_sets, r)) return rc;        // (r: start_index moves on like the results)
     if (p_in.traj_act_log && io.next_actions_dev)
         HIP_TRY(hipMemcpyAsync(p_in.traj_act_log + set * p_in.traj_out_envs, io.next_actions_dev, (size_t)h->n_envs * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                (hipStream_t)stream));
@@ -879,7 +969,18 @@ static int steps_launch(sgx_env *h, StepsParams &sp, KParams &p, const int32_t *
                 h->multi_step_attr = 1;
             }
             sp.k = p;
-            lane_steps_kernel<R, C><<<grid, 64 * (1 + KSTEP_EMITTERS), dyn, stream>>>(sp);
+            if (h->pool) {
+                if (dyn + sizeof(StepsLds<Geo<R, C>>) > 64 * 1024 && !h->multi_step_attr_pool) {
+                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&lane_steps_kernel_pool<R, C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
+                        (void)hipGetLastError();
+                        h->no_multi_step = 1;
+                        return;
+                    }
+                    h->multi_step_attr_pool = 1;
+                }
+                lane_steps_kernel_pool<R, C><<<grid, 64 * (1 + KSTEP_EMITTERS), dyn, stream>>>(sp, make_pool_params(h));
+            } else
+                lane_steps_kernel<R, C><<<grid, 64 * (1 + KSTEP_EMITTERS), dyn, stream>>>(sp);
             *ok = true;
         }
     });
@@ -917,7 +1018,8 @@ static int steps_launch(sgx_env *h, WaveStepsParams &sp, KParams &p, const int32
                 const unsigned grid = geo_grid<G>(p, w);
                 sp.k = p;
                 sp.barrier = want_barrier && (p.n_envs - p.env_first) % (G::WPB * G::GPW) == 0;
-                steps_kernel<R, C, KIND, VAR><<<grid, 64 * G::WPB, 0, stream>>>(sp);
+                if (h->pool) steps_kernel_pool<R, C, KIND, VAR><<<grid, 64 * G::WPB, 0, stream>>>(WaveStepsParamsPool{sp, make_pool_params(h)});
+                else steps_kernel<R, C, KIND, VAR><<<grid, 64 * G::WPB, 0, stream>>>(sp);
             });
         };
         if (kind == 0) launch(int_c<0>());
@@ -999,7 +1101,7 @@ static int play_steps(sgx_env *h, const KParams &p, const OutSets &sets, int32_t
     return SGX_OK;
 }
 
-static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_sets) {
+static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_sets, int64_t start_index_off, bool allow_pool) {
     KParams p = p_in;
     if (int rc = check_step_io(h, p)) return rc;
     int32_t w[8];
@@ -1007,6 +1109,9 @@ static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_s
     const hipStream_t st = (hipStream_t)stream;
     const bool full = p.io.fobs_dev || p.io.final_fobs_dev, original = (p.io.flags & SGX_STEP_ORIGINAL_CHANNELS) != 0;
     const bool compact = (p.io.flags & (SGX_STEP_COMPACT_OBS | SGX_STEP_COMPACT_MASK)) != 0;
+    // a handle with a start pool steps through the *_pool kernels (an auto-reset loads a pool record; every step writes start_index)
+    const bool pool = allow_pool && h->pool != nullptr && p.mode == 0;
+    const PoolParams pool_params = make_pool_params(h, start_index_off);
     if (compact) {
         // compact outputs: the 67-channel 'extended' observation as 4-bit codes / the mover's-perspective mask as bits, nothing else
         if (full || original || p.io.final_obs_dev || p.src_boards || (p.io.flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)))
@@ -1022,6 +1127,7 @@ static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_s
                     const unsigned grid = grid_for(p, 64, w);
                     const size_t dyn = 64 * (size_t)(p.rec_bytes + 16);
                     if (p.mode) lane_kernel<R, C, true><<<grid, 64, dyn, st>>>(p);
+                    else if (pool) lane_kernel_pool<R, C><<<grid, 64, dyn, st>>>(p, pool_params);
                     else lane_kernel<R, C, false><<<grid, 64, dyn, st>>>(p);
                 }
             })) return rc;
@@ -1034,6 +1140,8 @@ static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_s
     const bool mapped = (p.io.flags & (SGX_STEP_MASK_1D | SGX_STEP_MASK_STATE_COORDS)) || p.src_boards;
     if (mapped && (full || (original && !no_obs))) return fail(SGX_EINVAL, "state-coordinate masks and sgx_expand come with the 67-channel partial observation only%s");
     const int kind = compact ? 4 : no_obs ? 8 : (full ? 1 : 0) + (original ? 2 : 0);      // (sgx_layout.h: ObsKind)
+    if (pool && mapped && p.io.auto_reset)
+        return fail(SGX_EINVAL, "a handle with a start pool does not auto-reset in launches with state-coordinate masks (SGX_STEP_MASK_1D / _STATE_COORDS)%s");
     if (int rc = for_geometry(h, [&](auto r, auto c) {
             constexpr int R = decltype(r)::value, C = decltype(c)::value;
             auto launch = [&](auto kind_c, auto mapped_c) {
@@ -1044,7 +1152,18 @@ static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_s
                     using G = Geo<R, C, VAR>;
                     const unsigned grid = geo_grid<G>(p, w);
                     if (p.mode) observe_kernel<R, C, KIND, MAPPED, VAR><<<grid, 64 * G::WPB, 0, st>>>(p);
-                    else step_kernel<R, C, KIND, MAPPED, VAR><<<grid, 64 * G::WPB, 0, st>>>(p);
+                    else if constexpr (!MAPPED) {
+                        if (pool) {             // one step of steps_kernel_pool, writing the launch's own tensors
+                            WaveStepsParams sp;
+                            memset(&sp, 0, sizeof(sp));
+                            sp.k = p;
+                            sp.k.traj_res_envs = sp.k.traj_out_envs = 0;       // (a step of an sgx_step_traj call: launch_set_step has moved the pointers)
+                            sp.k.traj_act_log = nullptr;
+                            sp.n_steps = sp.n_sets = 1;
+                            sp.obs[0] = p.io.obs_dev; sp.fobs[0] = p.io.fobs_dev; sp.mask[0] = p.io.mask_dev;
+                            steps_kernel_pool<R, C, KIND, VAR><<<grid, 64 * G::WPB, 0, st>>>(WaveStepsParamsPool{sp, pool_params});
+                        } else step_kernel<R, C, KIND, MAPPED, VAR><<<grid, 64 * G::WPB, 0, st>>>(p);
+                    } else step_kernel<R, C, KIND, MAPPED, VAR><<<grid, 64 * G::WPB, 0, st>>>(p);
                 });
             };
             if (mapped) {
@@ -1389,7 +1508,9 @@ int step_single(sgx_env *h, const KParams &p, bool full, hipStream_t stream, boo
     if (int rc = for_geometry(h, [&](auto r, auto c) {
             constexpr int R = decltype(r)::value, C = decltype(c)::value;
             if constexpr (Geo<R, C>::LPG == 64 && !Geo<R, C>::WIDE && (R * C) % 4 == 0) {
-                if (full) single_kernel<R, C, 1><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, h->sync_count, h->sync_flag_dev, seq);
+                if (h->pool && full) single_kernel_pool<R, C, 1><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, make_pool_params(h), h->sync_count, h->sync_flag_dev, seq);
+                else if (h->pool) single_kernel_pool<R, C, 0><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, make_pool_params(h), h->sync_count, h->sync_flag_dev, seq);
+                else if (full) single_kernel<R, C, 1><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, h->sync_count, h->sync_flag_dev, seq);
                 else single_kernel<R, C, 0><<<(unsigned)h->n_envs, 64 * SINGLE_WAVES, 0, stream>>>(p, h->sync_count, h->sync_flag_dev, seq);
                 *launched = true;
             }
@@ -1782,6 +1903,8 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
     KParams p = make_params(h);
     p.mode = io->actions_dev ? 0 : 1;        // no actions: observe -- masks / observations of the given states, nothing is played
     p.io = *io;
+    if (h->pool && p.mode == 0 && io->auto_reset)
+        return fail(SGX_EINVAL, "sgx_step_states does not auto-reset on a handle with a start pool (its states are the caller's)%s");
     if (int rc = check_step_io(h, p)) return rc;
     // the general-state pass needs the flags even when the caller did not ask for them
     uint8_t *flags_dev = sanitised_dev;
@@ -1855,7 +1978,7 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
     };
     if (chains == 1) {
         if (int rc = launch_import(h, p, state_in_dev, player_in_dev, flags_dev, st)) return rc;
-        if (int rc = launch_step(h, p, stream)) return rc;
+        if (int rc = launch_step(h, p, stream, 1, 0, false)) return rc;      // (caller-provided states: no game starts here, no pool kernels)
         if (state_out_dev)
             if (int rc = launch_export(h, p, state_out_dev, player_out_dev, st)) return rc;
         return second_pass();
@@ -1867,7 +1990,7 @@ SGX_API int sgx_step_states(sgx_env *h, const int64_t *state_in_dev, const int8_
         pc.env_first = c * per;
         pc.n_envs = c == chains - 1 ? h->n_envs : (c + 1) * per;
         rc = launch_import(h, pc, state_in_dev, player_in_dev, flags_dev, h->chain_stream[c]);
-        if (rc == SGX_OK) rc = launch_step(h, pc, (void *)h->chain_stream[c]);
+        if (rc == SGX_OK) rc = launch_step(h, pc, (void *)h->chain_stream[c], 1, 0, false);
         if (rc == SGX_OK && state_out_dev) rc = launch_export(h, pc, state_out_dev, player_out_dev, h->chain_stream[c]);
     }
     rc = join_chains(h, chains, st, rc);     // (also after a failed launch: see sgx_rollout)

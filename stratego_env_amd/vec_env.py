@@ -162,6 +162,8 @@ class VecStrategoEnv:
         self._ring_pos = 0
         self._outputs_owner = self._outputs = None                 # tune_placement()
         self.placement_peak_extra_bytes = 0
+        self.start_index = None              # set_start_states(): int32 [N], the pool index of every env's current game
+        self._start_winners = None           # set_curriculum(): the table's `winner` column on the device
 
     # ---- lifecycle -----------------------------------------------------------------------------------
     def close(self):
@@ -281,6 +283,100 @@ class VecStrategoEnv:
                 except RuntimeError as e:          # (no memory for candidates next to another tenant: the plain tensors stay)
                     self.placement_report = {'failed': str(e)}
         return self.observe()
+
+    # ---- start pools: games that start from given positions (maenv:519-527, util.py:374-387 for a batch) -------------------------
+    @property
+    def start_pool_size(self):
+        """Number of records in the start pool (sgx_start_pool_size); 0 = none, games start from sampled setups."""
+        return int(self._L.sgx_start_pool_size(self._h))
+
+    def set_start_states(self, states, players=None, first_player='stored', restart_clock=False):
+        """From now on every game start that would sample a setup -- reset() without maps (also with env_select) and every auto-reset of
+        step() / step_sync() / rollout_steps() / rollout_trajectory(), also in the middle of a multi-step launch -- starts from one of
+        the given positions instead, drawn per (seed, env id, game number) on the device (sgx_set_start_pool).
+
+        states: int64 [n,34,R,C] in the reference layout with players int8 [n] (the movers), or a PackedStates / an outputs=False
+        VecStrategoEnv of the same variant (its records, `players` unused).  first_player: 'stored' = the position's mover, 'random' =
+        +1 / -1 drawn per game (maenv:523).  restart_clock: turn = 0 and max_turns = the variant's in every position (util.py:382-383).
+        The positions are COPIED: the argument may be changed or closed afterwards.  Raises ValueError naming the indices of positions
+        the packed record cannot carry (import_state_checked flags them `sanitised`) or whose game is over.  Explicit maps passed to
+        reset() still win; clear_start_states() goes back to sampled setups.  `start_index` (int32 [N]) holds the pool index of every
+        env's current game after the next reset() and after every step (reset() with explicit maps writes -1; such a game has no pool row).  Games already running
+        go on; call reset() to start all of them from the pool."""
+        if first_player not in ('stored', 'random'):
+            raise ValueError("first_player must be 'stored' or 'random'")
+        own = None
+        src = getattr(states, '_vec', states)
+        if isinstance(src, VecStrategoEnv):
+            pool, n = src, src.num_envs
+        else:
+            st = torch.as_tensor(states).to(device=self.device, dtype=torch.int64).contiguous()
+            if st.dim() != 4 or tuple(st.shape[1:]) != (NUM_STATE_LAYERS, self.R, self.Cc) or st.shape[0] < 1:
+                raise ValueError("states must be int64 [n, %d, %d, %d] with n >= 1" % (NUM_STATE_LAYERS, self.R, self.Cc))
+            n = int(st.shape[0])
+            if players is None:
+                raise ValueError("set_start_states: int64 states come with players int8 [n] (the movers)")
+            pl = torch.as_tensor(players).to(device=self.device, dtype=torch.int8).contiguous().reshape(-1)
+            if pl.numel() != n or bool(((pl != 1) & (pl != -1)).any()):
+                raise ValueError("players must be int8 [n] of +1 / -1")
+            own = pool = VecStrategoEnv(self.variant, n, device=self.device.index, seed=self.seed, human_inits=False, outputs=False)
+            san = torch.zeros((n,), dtype=torch.uint8, device=self.device)
+            pool.import_state_checked(st, pl, san)
+            bad = san.nonzero().reshape(-1).tolist()
+            if bad:
+                pool.close()
+                raise ValueError("set_start_states: the packed record cannot carry the positions %s (sanitised on import)" % bad)
+        try:
+            over = pool.env_info()[:, 2].nonzero().reshape(-1).tolist()
+            if over:
+                raise ValueError("set_start_states: the game of the positions %s is over" % over)
+            flags = (_lib.POOL_RANDOM_FIRST_PLAYER if first_player == 'random' else 0) | (_lib.POOL_RESTART_CLOCK if restart_clock else 0)
+            try:
+                with torch.cuda.device(self.device):
+                    _lib.check(self._L.sgx_set_start_pool(self._h, pool._h, n, flags), self._L)
+            except _lib.SgxError as e:
+                raise ValueError(str(e))
+        finally:
+            if own is not None:
+                own.close()
+        if self.start_index is None:
+            self.start_index = torch.full((self.num_envs,), -1, dtype=torch.int32, device=self.device)
+        _lib.check(self._L.sgx_set_start_index_out(self._h, _ptr(self.start_index)), self._L)
+        self._start_winners = None
+
+    def clear_start_states(self):
+        """Back to sampled setups (Gravon table / random placement): from here on bit for bit what an env that never had a pool does."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.sgx_set_start_pool(self._h, None, 0, 0), self._L)
+        _lib.check(self._L.sgx_set_start_index_out(self._h, None), self._L)
+        self.start_index = self._start_winners = None
+
+    def set_curriculum(self, path_or_pair):
+        """The reference's curriculum start states for a batch (curriculum_start_states_path, maenv:519-527; get_random_curriculum_init_fn,
+        util.py:374-387): a file load_curriculum_start_states reads (.npz / HDF5), or a (states, winners) pair.  Every game starts from a
+        position of the table with turn 0, the variant's max_turns and a random first mover; `start_winner` tells who the table says is
+        likely to win the env's current game ("player 1" of the reference's player_map; 0 for a game explicit maps started)."""
+        if isinstance(path_or_pair, (tuple, list)):
+            states, winners = path_or_pair
+        else:
+            from .multiagent_env import load_curriculum_start_states
+            states, winners = load_curriculum_start_states(path_or_pair)
+        states = np.asarray(states).reshape((-1, NUM_STATE_LAYERS, self.R, self.Cc)).astype(np.int64)
+        winners = np.asarray(winners).reshape(-1).astype(np.int8)
+        if winners.shape[0] != states.shape[0]:
+            raise ValueError("set_curriculum: %d states, %d winners" % (states.shape[0], winners.shape[0]))
+        # (the table's own movers are never used: the first mover is drawn per game, maenv:523)
+        self.set_start_states(states, np.ones(states.shape[0], dtype=np.int8), first_player='random', restart_clock=True)
+        self._start_winners = torch.from_numpy(winners).to(self.device)
+
+    @property
+    def start_winner(self):
+        """set_curriculum(): int8 [N], the table's `winner` of every env's current game (winners[start_index])."""
+        if self._start_winners is None:
+            raise ValueError("start_winner needs set_curriculum()")
+        idx = self.start_index.long()
+        w = self._start_winners[idx.clamp(min=0)]
+        return torch.where(idx >= 0, w, torch.zeros_like(w))       # (0: a game explicit maps started has no row of the table)
 
     def observe(self, raw=False, emit_obs=True, emit_mask=True):
         """_get_current_obs for every env (no state change); emit_obs / emit_mask = False skip those outputs."""
@@ -562,6 +658,8 @@ class VecStrategoEnv:
                 traj[k] = torch.zeros((T, N), dtype=dt, device=dev)
         if actions:
             traj['actions'] = torch.zeros((T, N), dtype=torch.int32, device=dev)
+        if results and self.start_index is not None:       # a start pool is set: the pool index of the game every slot's outputs belong to
+            traj['start_index'] = torch.full((T, N), -1, dtype=torch.int32, device=dev)
         return traj
 
     def rollout_trajectory(self, n_steps, traj, first_slot=0, emit_obs=True, emit_mask=True):
@@ -588,6 +686,15 @@ class VecStrategoEnv:
                          'invalid_action': ((N,), torch.uint8), 'ending_invalid': ((N,), torch.uint8)})
         if 'actions' in traj:
             want['actions'] = ((N,), torch.int32)
+        if self.start_index is not None and per_slot and 'start_index' not in traj:
+            # (per-slot results put step t's pool index at slot t too: the env's own [N] tensor has no room for that)
+            raise ValueError("a start pool is set: this trajectory needs traj['start_index'] (allocate it again with alloc_trajectory)")
+        if 'start_index' in traj:
+            if self.start_index is None:
+                raise ValueError("traj['start_index'] goes with a start pool (set_start_states)")
+            if not per_slot:
+                raise ValueError("traj['start_index'] goes with per-slot results (alloc_trajectory(results=True))")
+            want['start_index'] = ((N,), torch.int32)
         for k, (shape, dtype) in want.items():
             t = traj.get(k)
             if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (T,) + shape or t.dtype != dtype or not t.is_contiguous() or t.device != self.device):
@@ -596,6 +703,12 @@ class VecStrategoEnv:
         if not self._next_actions_fresh:
             self.sample_valid_actions()
         keep = (self.obs, self.mask, self.fobs, self.reward, self.done, self.player, self.invalid_action, self.ending_invalid)
+        keep_si = self.start_index
+
+        def point_start_index(t):
+            if keep_si is not None:
+                self.start_index = t
+                _lib.check(self._L.sgx_set_start_index_out(self._h, _ptr(t)), self._L)
 
         def views(slot):
             self.obs, self.mask, self.fobs = traj['obs'][slot], traj['mask'][slot], (traj['fobs'][slot] if 'fobs' in traj else None)
@@ -604,6 +717,8 @@ class VecStrategoEnv:
                 self.invalid_action, self.ending_invalid = traj['invalid_action'][slot], traj['ending_invalid'][slot]
         try:
             views(0)
+            if 'start_index' in traj:
+                point_start_index(traj['start_index'][0])          # (the library adds slot * num_envs, like for `done`)
             io = self._fill_io(self.next_actions, True, emit_obs, emit_mask, 0)
             t = _lib.SgxTrajIO()
             C.memmove(C.byref(t.io), C.byref(io), C.sizeof(_lib.SgxStepIO))
@@ -613,11 +728,15 @@ class VecStrategoEnv:
                 _lib.check(self._L.sgx_step_traj(self._h, C.byref(t), int(first_slot), n_steps, self._stream()), self._L)
         except BaseException:
             (self.obs, self.mask, self.fobs, self.reward, self.done, self.player, self.invalid_action, self.ending_invalid) = keep
+            point_start_index(keep_si)
             raise
         if n_steps == 0:
             (self.obs, self.mask, self.fobs, self.reward, self.done, self.player, self.invalid_action, self.ending_invalid) = keep
+            point_start_index(keep_si)
         else:
             views((first_slot + n_steps - 1) % T)
+            if 'start_index' in traj:                              # like `done`: the env's own view is the last slot written
+                point_start_index(traj['start_index'][(first_slot + n_steps - 1) % T])
         return traj
 
     def choose_actions(self, logits, temperature=1.0, mask=None, out=None):
@@ -649,7 +768,9 @@ class VecStrategoEnv:
     # ---- snapshots: the packed records of every game, in a pool without output tensors -------------------------------
     def snapshot(self, out=None):
         """Copy every game's packed record (boards, counters, game number: everything the counter RNG and the rules depend on)
-        into a pool of records without output tensors (`out`, or a new one): sgx_copy_envs.  restore() puts it back."""
+        into a pool of records without output tensors (`out`, or a new one): sgx_copy_envs.  restore() puts it back.
+        A start pool (set_start_states) is NOT part of a snapshot: the records carry the game numbers, so the restored games draw the
+        same start positions again only while the same pool is set."""
         snap = out if out is not None else VecStrategoEnv(self.variant, self.num_envs, device=self.device.index, seed=self.seed,
                                                           env_id_offset=self.env_id_offset, human_inits=False, outputs=False)
         with torch.cuda.device(self.device):

@@ -130,6 +130,7 @@ typedef struct sgx_step_io {
  *   sgx_reset            env_select_dev, p1_maps_dev, p2_maps_dev 1
  *   sgx_set_start_index_out   start_index_dev 4
  *   sgx_expand / sgx_copy_envs   src_index_dev, dst_index_dev 4
+ *   sgx_determinize              src_index_dev, hidden_dev 4
  *   sgx_mem_probe        ptr_dev 1024;   sgx_store_probe   ptr_dev 16
  * Change note: these rejections are new error returns for pointers that were never legal (the stores they guard were issued unchecked
  * before; only sgx_decode_obs and the compact path refused them); no struct or signature changed, so SGX_ABI_VERSION stays. */
@@ -561,6 +562,21 @@ int sgx_set_general_states(sgx_env *h, int32_t mode);
  * No reference counterpart beyond get_next_state itself. */
 int sgx_copy_envs(sgx_env *dst, const int32_t *dst_index_dev, sgx_env *src, const int32_t *src_index_dev, int64_t n, void *stream);
 int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_step_io *io, void *stream);
+
+/* Determinization for imperfect-information search (determinized MCTS, ISMCTS, PIMC rollouts): every slot i of `dst` becomes record
+ * src_index[i] of `src` (i when NULL) with the HIDDEN pieces of the observer's opponent dealt again, so that a search expanding from it does
+ * not see the true types.  observer: 0 = each record's mover, +1 / -1 = that player for every record.  Hidden cells are the opponent's
+ * pieces whose public board says 13 (unknown); their types are permuted uniformly over all assignments that keep the flag and the bombs on
+ * never-moved cells.  Nothing else of the record changes: public boards, never-moved bitmaps, scalars, recent moves, capture events and
+ * the observer's own pieces are copied bit for bit, so the observer's partial observation and valid-move mask are what they were.  The
+ * shuffle is keyed by (dst's seed, dst's env_id_offset + i, draw) on an RNG stream of its own: the same call gives the same worlds, another
+ * `draw` gives independent ones, and no draw of a rollout moves.  hidden_dev: int32 [dst's N] (NULL = not wanted) = number of hidden cells that
+ * were shuffled; -1 marks a record with a flag or a bomb on a moved hidden cell, which play cannot produce: it is copied unchanged.
+ * A sampled world agrees with everything the record tracks (what the reference's state tracks), NOT with the full move history: a piece that
+ * has acted in ways only some types can may still be dealt another type.  src == dst with a NULL index works in place; with an index it
+ * would race and is SGX_EINVAL, like an observer outside {-1, 0, 1}, a handle of another variant or a misaligned pointer (4 bytes).
+ * No reference counterpart. */
+int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer, uint64_t draw, int32_t *hidden_dev, void *stream);
 
 /* Per-env bookkeeping: int32 [N][4] = {turn count, game number, game_over, current player}. */
 int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream);

@@ -585,6 +585,98 @@ __global__ __launch_bounds__(256) void copy_records_kernel(int8_t *__restrict__ 
     for (int q = lane; q < rec_bytes / 16; q += 64) d[q] = s[q];
 }
 
+// sgx_determinize: record i of `dst` becomes record src_idx[i] of `src` with the hidden pieces of the observer's opponent dealt again -- a
+// world the observer cannot tell from the real one by anything the record holds.  Hidden cells H: an opponent piece whose
+// public board says SP_UNKNOWN, in ascending cell order; A = those that never moved, B = the rest.  Flags and bombs (types I) cannot have
+// moved: a Fisher-Yates shuffle of A hands its first |I| cells the types I, a second one over the rest of A followed by B hands out the
+// other types M.  A record with a flag or a bomb on a moved hidden cell cannot come from play: copied as it is, hidden[i] = -1.
+// One wave per record; the record layout enters as arguments (like copy_records_kernel / info_kernel), so one kernel serves every board.
+// Per wave in LDS: the record image | cell list L (uint16) | type list T (uint8); the whole record is read before anything is written, so
+// the identity call inside one handle is safe.
+__host__ __device__ constexpr int det_lds_bytes(int rec_bytes, int cells) { return rec_bytes + (((cells + 63) & ~63) * 3); }
+
+// Fisher-Yates over L[0, n): for k = n-1 .. 1 swap L[k] with L[rng_below(draw(t0 + k), k + 1)].  The draws of 64 k at a time are computed
+// by the lanes in parallel; the swaps are applied in order, every lane doing the same LDS accesses.
+__device__ inline void det_shuffle(uint16_t *L, const int n, const uint64_t seed, const uint64_t g, const uint64_t j, const uint32_t t0, const int lane) {
+    for (int hi = n - 1; hi >= 1;) {
+        const int base = hi & ~63, kk = base + lane;
+        const int dr = (int)rng_below(sgx_rng(seed, g, j, STREAM_DETERMINIZE, t0 + (uint32_t)kk), (uint32_t)kk + 1u);
+        for (int k = hi; k >= base && k >= 1; --k) {
+            const int r = __builtin_amdgcn_readlane(dr, k - base);
+            const uint16_t a = L[k], b = L[r];
+            L[k] = b;
+            L[r] = a;
+        }
+        hi = base - 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void determinize_kernel(int8_t *dst, const int8_t *src, const int32_t *__restrict__ src_idx,
+                                                          int32_t *__restrict__ hidden, const int64_t n, const uint64_t seed, const int64_t env_id_offset,
+                                                          const uint64_t draw, const int observer, const int S, const int st_off, const int sb,
+                                                          const int sc_off, const int rec_bytes, const int cells) {
+    extern __shared__ int4 det_lds[];
+    const int64_t i = blockIdx.x * (int64_t)(blockDim.x / 64) + threadIdx.x / 64;
+    if (i >= n) return;
+    const int lane = threadIdx.x & 63;
+    uint8_t *img = reinterpret_cast<uint8_t *>(det_lds) + (threadIdx.x / 64) * det_lds_bytes(rec_bytes, cells);   // (a multiple of 64 bytes)
+    uint16_t *L = reinterpret_cast<uint16_t *>(img + rec_bytes);
+    uint8_t *T = img + rec_bytes + 2 * ((cells + 63) & ~63);
+    const int4 *s = reinterpret_cast<const int4 *>(src + (int64_t)(src_idx ? src_idx[i] : i) * rec_bytes);
+    for (int q = lane; q < rec_bytes / 16; q += 64) reinterpret_cast<int4 *>(img)[q] = s[q];
+    wave_sync<Geo<10, 10>>();
+    const int flags = reinterpret_cast<const int4 *>(img + sc_off)[0].y;
+    const int opp = (observer ? observer : ((flags & F_PLAYER_M1) ? -1 : 1)) == 1 ? 1 : 0;      // player index of the observer's opponent
+    uint8_t *pieces = img + (B_PIECES + opp) * S;
+    const uint8_t *po = img + (B_PO + opp) * S;
+    const uint32_t *still = reinterpret_cast<const uint32_t *>(img + st_off + opp * sb);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    // first pass: |A|, |I| and whether a flag or a bomb sits on a moved hidden cell
+    int nA = 0, nI = 0, nH = 0;
+    bool bad = false;
+    for (int c0 = 0; c0 < cells; c0 += 64) {
+        const int cell = c0 + lane, cc = cell < cells ? cell : 0;                 // (all three loads in flight at once)
+        const int t = pieces[cc], p = po[cc];
+        const uint32_t w = still[cc >> 5];
+        const bool hid = cell < cells && t != 0 && p == SP_UNKNOWN;
+        const bool st = hid && ((w >> (cell & 31)) & 1u) != 0;
+        const bool fb = hid && (t == SP_FLAG || t == SP_BOMB);
+        nA += __popcll(__ballot(st));
+        nI += __popcll(__ballot(fb));
+        nH += __popcll(__ballot(hid));
+        bad = bad || __ballot(fb && !st) != 0;
+    }
+    if (!bad && nH > 0) {
+        // second pass: L = A ++ B (cells), T = I ++ M (types), each part in ascending cell order
+        int atA = 0, atB = nA, atI = 0, atM = nI;
+        for (int c0 = 0; c0 < cells; c0 += 64) {
+            const int cell = c0 + lane, cc = cell < cells ? cell : 0;
+            const int t = pieces[cc], p = po[cc];
+            const uint32_t w = still[cc >> 5];
+            const bool hid = cell < cells && t != 0 && p == SP_UNKNOWN;
+            const bool st = hid && ((w >> (cell & 31)) & 1u) != 0;
+            const bool fb = hid && (t == SP_FLAG || t == SP_BOMB);
+            const unsigned long long bA = __ballot(st), bB = __ballot(hid && !st), bI = __ballot(fb), bM = __ballot(hid && !fb);
+            if (hid) {
+                L[st ? atA + __popcll(bA & below) : atB + __popcll(bB & below)] = (uint16_t)cell;
+                T[fb ? atI + __popcll(bI & below) : atM + __popcll(bM & below)] = (uint8_t)t;
+            }
+            atA += __popcll(bA); atB += __popcll(bB); atI += __popcll(bI); atM += __popcll(bM);
+        }
+        wave_sync<Geo<10, 10>>();
+        const uint64_t g = (uint64_t)(env_id_offset + i);
+        det_shuffle(L, nA, seed, g, draw, 0u, lane);
+        wave_sync<Geo<10, 10>>();
+        det_shuffle(L + nI, nH - nI, seed, g, draw, 1024u, lane);          // (cells <= 1,024: the two stages never share a counter)
+        wave_sync<Geo<10, 10>>();
+        for (int q = lane; q < nH; q += 64) pieces[L[q]] = T[q];
+        wave_sync<Geo<10, 10>>();
+    }
+    int4 *d = reinterpret_cast<int4 *>(dst + i * (int64_t)rec_bytes);
+    for (int q = lane; q < rec_bytes / 16; q += 64) d[q] = reinterpret_cast<const int4 *>(img)[q];
+    if (lane == 0 && hidden) hidden[i] = bad ? -1 : nH;
+}
+
 __global__ void info_kernel(const int8_t *__restrict__ boards, int rec_bytes, int sc_off, int32_t *__restrict__ out, int64_t n) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;

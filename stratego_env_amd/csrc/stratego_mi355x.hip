@@ -2049,6 +2049,26 @@ SGX_API int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
     return launch_step(dst, p, stream);
 }
 
+SGX_API int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer, uint64_t draw, int32_t *hidden_dev, void *stream) {
+    if (!dst || !src) return fail(SGX_EINVAL, "handle is NULL%s");
+    if (int rc = same_variant(dst, src)) return rc;
+    if (!src_index_dev && src->n_envs < dst->n_envs) return fail(SGX_EINVAL, "without src_index_dev the source handle needs at least as many envs%s");
+    // wave i reads record src_index[i] while another wave of the same launch rewrites that record (the identity call is safe: a wave holds
+    // its whole record in LDS before it writes)
+    if (src == dst && src_index_dev)
+        return fail(SGX_EINVAL, "sgx_determinize: src == dst with an index array would race; determinize into a second handle%s");
+    if (observer < -1 || observer > 1) return fail(SGX_EINVAL, "sgx_determinize: observer must be 0 (each record's mover), +1 or -1%s");
+    if (int rc = check_aligned("sgx_determinize", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_determinize", "hidden_dev", hidden_dev, 4)) return rc;
+    SGX_ON_DEVICE(dst->device);
+    const int cells = dst->cfg.rows * dst->cfg.cols, S = (cells + 3) & ~3, sb = (((cells + 7) / 8) + 15) & ~15;
+    determinize_kernel<<<(unsigned)((dst->n_envs + 3) / 4), 256, 4 * det_lds_bytes(dst->rec_bytes, cells), (hipStream_t)stream>>>(
+        dst->boards, src->boards, src_index_dev, hidden_dev, dst->n_envs, dst->seed, dst->env_id_offset, draw, observer, S, dst->sc_off - 2 * sb, sb,
+        dst->sc_off, dst->rec_bytes, cells);
+    HIP_TRY(hipGetLastError());
+    return SGX_OK;
+}
+
 SGX_API int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream) {
     if (!h || !info_dev) return fail(SGX_EINVAL, "NULL argument%s");
     if (int rc = check_aligned("sgx_get_env_info", "info_dev", info_dev, 16)) return rc;      // (info_kernel: one int4 store per game)

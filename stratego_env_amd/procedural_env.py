@@ -379,9 +379,10 @@ class BatchedStrategoProceduralEnv:
         return self.get_action_spatial_index_from_positions(sr, sc, er, ec)
 
     # ---- packed states: search nodes kept in the library's records (no int64 import / export per call) ---------------
-    def new_packed(self, n=None):
-        """An empty pool of `n` packed states of this variant (default: batch_size)."""
-        return PackedStates(self.variant, self.batch_size if n is None else n, self.device)
+    def new_packed(self, n=None, seed=0, env_id_offset=0):
+        """An empty pool of `n` packed states of this variant (default: batch_size).  seed / env_id_offset key the pool's own random
+        draws (PackedStates.determinize)."""
+        return PackedStates(self.variant, self.batch_size if n is None else n, self.device, seed=seed, env_id_offset=env_id_offset)
 
     def pack(self, states, players, out=None):
         """int64 [n,34,R,C] + players -> PackedStates (`out` or a new pool); `sanitised` uint8 [n] reports altered states."""
@@ -392,6 +393,22 @@ class BatchedStrategoProceduralEnv:
             raise ValueError("state is not one the packed record can carry (unreachable by play)")
         return out
 
+    def determinize(self, states, players, observer=0, draw=0):
+        """One sampled world per state for imperfect-information search: the hidden pieces of the observer's opponent dealt again
+        (PackedStates.determinize: pack -> determinize into a scratch pool -> unpack, for callers on the reference layout).
+        observer: 0 = each state's `players` entry, +1 / -1 = that player for all.  -> (states int64 [n,34,R,C], hidden int32 [n]);
+        hidden[i] = -1 marks a state with a flag or a bomb on a moved hidden cell, returned unchanged.  No reference counterpart."""
+        src = self.pack(states, players)
+        try:
+            dst = self.new_packed(src.n)
+            try:
+                hidden = dst.determinize(src, observer=observer, draw=draw)
+                return dst.unpack()[0], hidden
+            finally:
+                dst.close()
+        finally:
+            src.close()
+
     def close(self):
         self._vec.close()
 
@@ -401,8 +418,9 @@ class PackedStates:
     layout), for tree-search callers of get_next_state (penv:148-155): nodes are expanded pool-to-pool with `expand`, copied with
     `copy_from`, and only converted to the reference layout when somebody wants to look at them (`unpack`)."""
 
-    def __init__(self, version, n, device=0):
-        self._vec = VecStrategoEnv(version, n, device=device, human_inits=False, outputs=False)     # records only: no observation / mask tensors
+    def __init__(self, version, n, device=0, seed=0, env_id_offset=0):
+        # records only: no observation / mask tensors
+        self._vec = VecStrategoEnv(version, n, device=device, seed=seed, env_id_offset=env_id_offset, human_inits=False, outputs=False)
         self.n = int(n)
         self.device = self._vec.device
         self.sanitised = torch.zeros((self.n,), dtype=torch.uint8, device=self.device)
@@ -447,6 +465,28 @@ class PackedStates:
             _lib.check(vec._L.sgx_expand(vec._h, parents._vec._h, None if pi is None else pi.data_ptr(), io, vec._stream()), vec._L)
         vec._next_actions_fresh = False
         return vec.invalid_action == 0, vec.player
+
+    def determinize(self, src, src_index=None, observer=0, draw=0):
+        """Sample a world the observer cannot tell from the real one into every slot i of this pool: self[i] = src[src_index[i]] with the
+        hidden pieces of the observer's opponent (its pieces the public board shows as unknown) dealt again, uniformly over all assignments
+        that keep the flag and the bombs on never-moved cells.  Everything else of the record -- and so the observer's partial observation and
+        valid moves -- stays what it was.  `src`: a PackedStates (this pool itself for an in-place call without src_index) or a live
+        VecStrategoEnv of the same variant; observer: 0 = each record's mover, +1 / -1 = that player for all; the shuffle is keyed by
+        (this pool's seed, its env_id_offset + i, draw), so another `draw` gives independent worlds of the same roots.
+        -> hidden int32 [n]: the number of hidden cells shuffled, -1 where a flag or a bomb sits on a moved hidden cell (play cannot produce
+        that; the record is copied unchanged).  The worlds agree with the record's public layers, not with the full move history."""
+        vec = self._vec
+        src_vec = src._vec if isinstance(src, PackedStates) else src
+        if src_vec is vec and src_index is not None:
+            raise ValueError("in-place determinization through src_index would race (a record may be overwritten before it is read): "
+                             "determinize into another pool")
+        si = None if src_index is None else torch.as_tensor(src_index).to(device=self.device, dtype=torch.int32).reshape(self.n).contiguous()
+        hidden = torch.empty((self.n,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(vec._L.sgx_determinize(vec._h, src_vec._h, None if si is None else si.data_ptr(), int(observer),
+                                              int(draw) & 0xFFFFFFFFFFFFFFFF, hidden.data_ptr(), vec._stream()), vec._L)
+        vec._next_actions_fresh = False
+        return hidden
 
     def valid_moves_as_1d_mask(self):
         out = torch.empty((self.n, self._vec.variant.action_size), dtype=torch.uint8, device=self.device)

@@ -428,36 +428,6 @@ __global__ __launch_bounds__(256) void import_kernel(const KParams P, const int6
 // Threads per state: 128 / 192 / 256 measured 654 / 628 / 636 us per 65,536 Barrage states in one process (tools/states_ab.py).
 // (get_next_state / is_move_valid_*: three waves per state; the variants whose ONE stepping wave also emits a mask or an observation
 // want more blocks per CU instead: 1-D masks 463 us with 128 threads, 592 us with 192)
-// The workgroup-shared observation tables of a step of kind KIND (the staging of game_kernel_body, sgx_step.h, for a block of `nthreads`)
-template <class G, int KIND>
-__device__ inline void stage_kind_tables(const KParams &P, uint8_t *shared, int tid, int nthreads) {
-    using PS = typename ObsKind<KIND>::P;
-    using FS = typename ObsKind<KIND>::F;
-    constexpr bool FULL = ObsKind<KIND>::FULL, ORIG = ObsKind<KIND>::ORIG;
-    const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
-    if constexpr (ORIG) {
-        float *lut_s = reinterpret_cast<float *>(shared);
-        const f32x4 *lsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0)]);
-        for (int i = tid; i < LUT_DWORDS / 4; i += nthreads) reinterpret_cast<f32x4 *>(lut_s)[i] = lsrc[i];
-        build_quad_table<G, PS>(reinterpret_cast<uint32_t *>(lut_s + LUT_DWORDS), tid, nthreads);
-        if constexpr (FULL) {
-            const f32x4 *fsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0) + 1]);
-            for (int i = tid; i < LUT_DWORDS / 4; i += nthreads) reinterpret_cast<f32x4 *>(lut_s + OBS_TAB_DWORDS)[i] = fsrc[i];
-            build_quad_table<G, FS>(reinterpret_cast<uint32_t *>(lut_s + OBS_TAB_DWORDS + LUT_DWORDS), tid, nthreads);
-        }
-    } else {
-        constexpr int NP = tmpl_lds_bytes<G, KIND>(false), NF = FULL ? tmpl_lds_bytes<G, KIND>(true) : 0;
-        const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
-        for (int i = tid; i < NP / 16; i += nthreads) reinterpret_cast<int4 *>(shared)[i] = tp[i];
-        if constexpr (FULL) {
-            const int4 *tf = reinterpret_cast<const int4 *>(P.tab->tmpl[(raw ? 2 : 0) + 1]);
-            for (int i = tid; i < NF / 16; i += nthreads) reinterpret_cast<int4 *>(shared + NP)[i] = tf[i];
-        }
-        const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
-        for (int i = tid; i < CODETAB_BYTES / 16; i += nthreads) reinterpret_cast<int4 *>(shared + NP + NF)[i] = ct[i];
-    }
-}
-
 template <bool MAPPED, bool OBS>
 constexpr int states_threads() { return (!MAPPED && !OBS) ? 192 : 128; }
 // VAR = 1: the second pass of sgx_step_states over the states the first pass had to alter (sanitised[env] != 0; every other block leaves at
@@ -490,17 +460,10 @@ __global__ __launch_bounds__((states_threads<MAPPED, OBS>())) void states_kernel
         env = P.env_first + group_of_block(P);
         if (env >= P.n_envs) return;
     }
-    {   // the step's workgroup-shared tables (game_kernel_body): default-code templates, code table, obstacle map, combat outcomes
-        if constexpr (KINDX >= 0) {
-            stage_kind_tables<G, KIND>(P, shared, tid, NT);
-        } else if constexpr (OBS) {
-            const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
-            constexpr int NP = tmpl_lds_bytes<G, 0>(false);
-            const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
-            for (int i = tid; i < NP / 16; i += NT) reinterpret_cast<int4 *>(shared)[i] = tp[i];
-            const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
-            for (int i = tid; i < CODETAB_BYTES / 16; i += NT) reinterpret_cast<int4 *>(shared + NP)[i] = ct[i];
-        }
+    {   // the step's workgroup-shared tables: stage_tables (sgx_step.h) in two halves -- no observation tables with OBS = false (the step runs as an 'original'
+        // kind over a 16-byte `shared` then), and loops of its own for the obstacle map and the combat table
+        // (through stage_tables states_kernel<10,10,true,false,0> took 71 VGPRs for 70 and states_kernel<15,15,false,true,1> 251 for 249)
+        if constexpr (OBS) stage_obs_tables<G, KIND>(P, shared, tid, NT);
         for (int i = tid; i < G::S / 4; i += NT) reinterpret_cast<int *>(obst_s)[i] = reinterpret_cast<const int *>(P.tab->obstacles)[i];
         for (int i = tid; i < COMBAT_BYTES / 4; i += NT) reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
     }

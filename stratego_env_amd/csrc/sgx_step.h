@@ -715,6 +715,48 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
 #endif
 }
 
+// The workgroup's shared tables (L2-resident sources), staged by all `nthreads` threads of the block before its barrier -- the one text every
+// wave-per-game kernel runs.  stage_obs_tables fills `shared` with the observation tables of kind KIND: the default-code templates and the
+// code table, or the LUTs and quad tables of the 'original' channel kinds; nothing for a kind that renders no observation.
+template <class G, int KIND, class KP>
+__device__ __forceinline__ void stage_obs_tables(const KP &P, uint8_t *shared, int tid, int nthreads) {
+    if constexpr (!ObsKind<KIND>::NOOBS) {
+        using PS = typename ObsKind<KIND>::P;
+        using FS = typename ObsKind<KIND>::F;
+        constexpr bool FULL = ObsKind<KIND>::FULL;
+        const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
+        if constexpr (ObsKind<KIND>::ORIG) {
+            float *lut_s = reinterpret_cast<float *>(shared);
+            const f32x4 *lsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0)]);
+            for (int i = tid; i < LUT_DWORDS / 4; i += nthreads) reinterpret_cast<f32x4 *>(lut_s)[i] = lsrc[i];
+            build_quad_table<G, PS>(reinterpret_cast<uint32_t *>(lut_s + LUT_DWORDS), tid, nthreads);
+            if constexpr (FULL) {
+                const f32x4 *fsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0) + 1]);
+                for (int i = tid; i < LUT_DWORDS / 4; i += nthreads) reinterpret_cast<f32x4 *>(lut_s + OBS_TAB_DWORDS)[i] = fsrc[i];
+                build_quad_table<G, FS>(reinterpret_cast<uint32_t *>(lut_s + OBS_TAB_DWORDS + LUT_DWORDS), tid, nthreads);
+            }
+        } else {
+            constexpr int NP = tmpl_lds_bytes<G, KIND>(false), NF = FULL ? tmpl_lds_bytes<G, KIND>(true) : 0;
+            const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
+            for (int i = tid; i < NP / 16; i += nthreads) reinterpret_cast<int4 *>(shared)[i] = tp[i];
+            if constexpr (FULL) {
+                const int4 *tf = reinterpret_cast<const int4 *>(P.tab->tmpl[(raw ? 2 : 0) + 1]);
+                for (int i = tid; i < NF / 16; i += nthreads) reinterpret_cast<int4 *>(shared + NP)[i] = tf[i];
+            }
+            const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
+            for (int i = tid; i < CODETAB_BYTES / 16; i += nthreads) reinterpret_cast<int4 *>(shared + NP + NF)[i] = ct[i];
+        }
+    }
+}
+// stage_tables: those, then into `obst_s` the obstacle map and the combat outcome table
+template <class G, int KIND, class KP>
+__device__ __forceinline__ void stage_tables(const KP &P, uint8_t *shared, uint8_t *obst_s, int tid, int nthreads) {
+    stage_obs_tables<G, KIND>(P, shared, tid, nthreads);
+    for (int i = tid; i < G::S / 4; i += nthreads) reinterpret_cast<int *>(obst_s)[i] = reinterpret_cast<const int *>(P.tab->obstacles)[i];
+    for (int i = tid; i < COMBAT_BYTES / 4; i += nthreads)
+        reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
+}
+
 // KIND bit 0: also renders the fully-observable observation (BOTH_OBSERVATIONS / FULLY_OBSERVABLE modes, maenv:477-492);
 // KIND bit 1: obs_channel_mode 'original' (32/33 value channels) instead of 'extended' (67/79 one-hot channels);
 // KIND bit 2 (alone: KIND 4): compact outputs -- the partial 'extended' kind whose observation / mask may leave as codes / bits
@@ -722,9 +764,6 @@ template <int R_, int C_, int KIND, bool MAPPED, int VAR = 0>
 __device__ __forceinline__ void game_kernel_body(const KParams &P) {
     using G = Geo<R_, C_, VAR>;
     static_assert(VAR == 0 || (VAR == 2 && ObsKind<KIND>::NOOBS), "two games per wave: the no-observation kinds only");
-    using PS = typename ObsKind<KIND>::P;
-    using FS = typename ObsKind<KIND>::F;
-    constexpr bool FULL = ObsKind<KIND>::FULL, ORIG = ObsKind<KIND>::ORIG;
     __shared__ Lds<G, ObsKind<KIND>::NIB_CH> LW[G::WPB * G::GPW];
     __shared__ alignas(16) uint8_t shared[shared_table_bytes<G, KIND>()];
     __shared__ alignas(16) uint8_t obst_s[G::OBST_BYTES + COMBAT_BYTES];    // obstacle map, then the combat outcome table
@@ -733,34 +772,7 @@ __device__ __forceinline__ void game_kernel_body(const KParams &P) {
     // The game's record and action are requested FIRST: the reads fly while the workgroup stages its shared tables (another
     // global round trip) and waits at the barrier -- the two round trips used to follow each other.
     const GameInput in = load_game<G, MAPPED>(P, env, lane);
-    // ---- the workgroup's shared tables (L2-resident sources)
-    const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
-    if constexpr (ObsKind<KIND>::NOOBS) {
-        // nothing to render: only the obstacle map and the combat table below
-    } else if constexpr (ORIG) {
-        float *lut_s = reinterpret_cast<float *>(shared);
-        const f32x4 *lsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0)]);
-        for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s)[i] = lsrc[i];
-        build_quad_table<G, PS>(reinterpret_cast<uint32_t *>(lut_s + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
-        if constexpr (FULL) {
-            const f32x4 *fsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0) + 1]);
-            for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s + OBS_TAB_DWORDS)[i] = fsrc[i];
-            build_quad_table<G, FS>(reinterpret_cast<uint32_t *>(lut_s + OBS_TAB_DWORDS + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
-        }
-    } else {
-        constexpr int NP = tmpl_lds_bytes<G, KIND>(false), NF = FULL ? tmpl_lds_bytes<G, KIND>(true) : 0;
-        const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
-        for (int i = threadIdx.x; i < NP / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared)[i] = tp[i];
-        if constexpr (FULL) {
-            const int4 *tf = reinterpret_cast<const int4 *>(P.tab->tmpl[(raw ? 2 : 0) + 1]);
-            for (int i = threadIdx.x; i < NF / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP)[i] = tf[i];
-        }
-        const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
-        for (int i = threadIdx.x; i < CODETAB_BYTES / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP + NF)[i] = ct[i];
-    }
-    for (int i = threadIdx.x; i < G::S / 4; i += 64 * G::WPB) reinterpret_cast<int *>(obst_s)[i] = reinterpret_cast<const int *>(P.tab->obstacles)[i];
-    for (int i = threadIdx.x; i < COMBAT_BYTES / 4; i += 64 * G::WPB)
-        reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
+    stage_tables<G, KIND>(P, shared, obst_s, threadIdx.x, 64 * G::WPB);
     __syncthreads();   // from here on every wave works on its own game
     if (env < P.n_envs) env_step<R_, C_, KIND, MAPPED, false, VAR>(P, LW[slot], shared, obst_s, env, lane, in);
 }
@@ -835,103 +847,28 @@ struct WaveStepsParamsPool {
     WaveStepsParams w;
     PoolParams pool;
 };
-__device__ __forceinline__ const SGX_KERNARG WaveStepsParams *wsp_of(const SGX_KERNARG WaveStepsParams *p) { return p; }
-__device__ __forceinline__ const SGX_KERNARG WaveStepsParams *wsp_of(const SGX_KERNARG WaveStepsParamsPool *p) { return &p->w; }
-// the body of steps_kernel_pool (TWIN: steps_kernel below, whose table staging this restates)
-template <int R_, int C_, int KIND, int VAR, class SPT = WaveStepsParamsPool>
-__device__ __forceinline__ void steps_body(const SPT &SP) {
-    constexpr bool POOL = true;
-    using G = Geo<R_, C_, VAR>;
-    static_assert(VAR == 0 || (VAR == 2 && ObsKind<KIND>::NOOBS), "two games per wave: the no-observation kinds only");
-    using PS = typename ObsKind<KIND>::P;
-    using FS = typename ObsKind<KIND>::F;
-    constexpr bool FULL = ObsKind<KIND>::FULL, ORIG = ObsKind<KIND>::ORIG;
-    // The parameters are read through the kernel-argument segment's address IN ITS OWN ADDRESS SPACE (SGX_KERNARG, sgx_layout.h), and the loop
-    // below hides that address from the optimiser once per step: otherwise every field env_step looks at is hoisted out of the loop and held
-    // in scalar registers for its whole length (106 of 106 SGPRs, 324 bytes of scratch); re-read per step they cost a few scalar loads from
-    // the constant cache.  (Through a generic pointer -- the first version of this kernel -- the re-reads were 17 VECTOR loads per game and
-    // step, each followed by a wait for everything the wave had in flight, its observation stores included: 5x5 95 -> 76 us per step, 15x15
-    // 369 -> 311, 6x6 111 -> 99, 10x10 246 -> 241 on one set of buffers, tools/lib_ab.py.)
+// The multi-step kernels read their parameters through the kernel-argument segment's address IN ITS OWN ADDRESS SPACE (SGX_KERNARG, sgx_layout.h), and
+// their loops hide that address from the optimiser once per step: otherwise every field env_step looks at is hoisted out of the loop and held
+// in scalar registers for its whole length (106 of 106 SGPRs, 324 bytes of scratch); re-read per step they cost a few scalar loads from
+// the constant cache.  (Through a generic pointer -- the first version of this kernel -- the re-reads were 17 VECTOR loads per game and
+// step, each followed by a wait for everything the wave had in flight, its observation stores included: 5x5 95 -> 76 us per step, 15x15
+// 369 -> 311, 6x6 111 -> 99, 10x10 246 -> 241 on one set of buffers, tools/lib_ab.py.)
+template <class SPT>
+__device__ __forceinline__ const SGX_KERNARG SPT *kernarg_of(const SPT &SP) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const SGX_KERNARG SPT *top = (const SGX_KERNARG SPT *)__builtin_amdgcn_kernarg_segment_ptr();
+    return (const SGX_KERNARG SPT *)__builtin_amdgcn_kernarg_segment_ptr();
 #else
-    const SPT *top = &SP;                         // (host pass of the single-source compile: never executed)
+    return &SP;                                   // (host pass of the single-source compile: never executed)
 #endif
-    const SGX_KERNARG WaveStepsParams *spp = wsp_of(top);
-    const SGX_KERNARG KParams &P = spp->k;
-    __shared__ Lds<G, ObsKind<KIND>::NIB_CH> LW[G::WPB * G::GPW];
-    __shared__ alignas(16) uint8_t shared[shared_table_bytes<G, KIND>()];
-    __shared__ alignas(16) uint8_t obst_s[G::OBST_BYTES + COMBAT_BYTES];
-    const int lane = threadIdx.x & (G::LPG - 1), slot = threadIdx.x / G::LPG;
-    const int64_t env = P.env_first + group_of_block(P) * (G::WPB * G::GPW) + slot;
-    const GameInput in = load_game<G, false>(P, env, lane);
-    const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
-    if constexpr (ObsKind<KIND>::NOOBS) {
-    } else if constexpr (ORIG) {
-        float *lut_s = reinterpret_cast<float *>(shared);
-        const f32x4 *lsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0)]);
-        for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s)[i] = lsrc[i];
-        build_quad_table<G, PS>(reinterpret_cast<uint32_t *>(lut_s + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
-        if constexpr (FULL) {
-            const f32x4 *fsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0) + 1]);
-            for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s + OBS_TAB_DWORDS)[i] = fsrc[i];
-            build_quad_table<G, FS>(reinterpret_cast<uint32_t *>(lut_s + OBS_TAB_DWORDS + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
-        }
-    } else {
-        constexpr int NP = tmpl_lds_bytes<G, KIND>(false), NF = FULL ? tmpl_lds_bytes<G, KIND>(true) : 0;
-        const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
-        for (int i = threadIdx.x; i < NP / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared)[i] = tp[i];
-        if constexpr (FULL) {
-            const int4 *tf = reinterpret_cast<const int4 *>(P.tab->tmpl[(raw ? 2 : 0) + 1]);
-            for (int i = threadIdx.x; i < NF / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP)[i] = tf[i];
-        }
-        const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
-        for (int i = threadIdx.x; i < CODETAB_BYTES / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP + NF)[i] = ct[i];
-    }
-    for (int i = threadIdx.x; i < G::S / 4; i += 64 * G::WPB) reinterpret_cast<int *>(obst_s)[i] = reinterpret_cast<const int *>(P.tab->obstacles)[i];
-    for (int i = threadIdx.x; i < COMBAT_BYTES / 4; i += 64 * G::WPB)
-        reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
-    __syncthreads();   // from here on every wave works on its own game, for all n_steps
-    if (env >= P.n_envs) return;
-    int set = spp->first_set;
-    const int n_steps = spp->n_steps;
-    if constexpr (POOL) {
-        StepCarryPool carry{};
-        // a handle with a start pool: ONE copy of the step (env_step<PERSIST_ = 3, POOL>) plays the first step and the later ones -- and, with
-        // n_steps = 1, the launches of sgx_step / sgx_rollout's chains: the pool costs one instantiation per observation kind
-        for (int t = 0; t < n_steps; ++t) {
-            const SGX_KERNARG SPT *tp = top;
-            int lane_t = lane, slot_t = slot;
-            asm volatile("" : "+s"(tp), "+v"(lane_t), "+v"(slot_t));
-            const SGX_KERNARG WaveStepsParams *sp = wsp_of(tp);
-            if (t && sp->barrier) __builtin_amdgcn_s_barrier();
-            steps_outputs_of(sp, set, carry);
-            carry.first = t == 0;
-            env_step<R_, C_, KIND, false, false, VAR, 3, true>(sp->k, LW[slot_t], shared, obst_s, env, lane_t, in, nullptr, nullptr, &carry, t == n_steps - 1, &tp->pool);
-            set = set + 1 == sp->n_sets ? 0 : set + 1;
-        }
-    }
 }
-// (steps_kernel is its own text, not a call of steps_body: as a call three of its instantiations paid a VGPR or 8 bytes of scratch.
-//  TWIN: steps_body below restates the table staging for steps_kernel_pool.)
+// steps_kernel and steps_kernel_pool share the table staging and the parameter access, and deliberately nothing after the barrier: steps_kernel
+// keeps a copy of the first step of its own and its own loop (as a call of one shared body three of its instantiations paid a VGPR or 8 bytes
+// of scratch; with the first step inside the loop the record's registers stay live across it).
 template <int R_, int C_, int KIND, int VAR = 0>
 __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd<Geo<R_, C_, VAR>, KIND>())) void steps_kernel(const WaveStepsParams SP) {
     using G = Geo<R_, C_, VAR>;
     static_assert(VAR == 0 || (VAR == 2 && ObsKind<KIND>::NOOBS), "two games per wave: the no-observation kinds only");
-    using PS = typename ObsKind<KIND>::P;
-    using FS = typename ObsKind<KIND>::F;
-    constexpr bool FULL = ObsKind<KIND>::FULL, ORIG = ObsKind<KIND>::ORIG;
-    // The parameters are read through the kernel-argument segment's address IN ITS OWN ADDRESS SPACE (SGX_KERNARG, sgx_layout.h), and the loop
-    // below hides that address from the optimiser once per step: otherwise every field env_step looks at is hoisted out of the loop and held
-    // in scalar registers for its whole length (106 of 106 SGPRs, 324 bytes of scratch); re-read per step they cost a few scalar loads from
-    // the constant cache.  (Through a generic pointer -- the first version of this kernel -- the re-reads were 17 VECTOR loads per game and
-    // step, each followed by a wait for everything the wave had in flight, its observation stores included: 5x5 95 -> 76 us per step, 15x15
-    // 369 -> 311, 6x6 111 -> 99, 10x10 246 -> 241 on one set of buffers, tools/lib_ab.py.)
-#if defined(__HIP_DEVICE_COMPILE__)
-    const SGX_KERNARG WaveStepsParams *spp = (const SGX_KERNARG WaveStepsParams *)__builtin_amdgcn_kernarg_segment_ptr();
-#else
-    const WaveStepsParams *spp = &SP;             // (host pass of the single-source compile: never executed)
-#endif
+    const SGX_KERNARG WaveStepsParams *spp = kernarg_of(SP);
     const SGX_KERNARG KParams &P = spp->k;
     __shared__ Lds<G, ObsKind<KIND>::NIB_CH> LW[G::WPB * G::GPW];
     __shared__ alignas(16) uint8_t shared[shared_table_bytes<G, KIND>()];
@@ -939,32 +876,7 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
     const int lane = threadIdx.x & (G::LPG - 1), slot = threadIdx.x / G::LPG;
     const int64_t env = P.env_first + group_of_block(P) * (G::WPB * G::GPW) + slot;
     const GameInput in = load_game<G, false>(P, env, lane);
-    const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
-    if constexpr (ObsKind<KIND>::NOOBS) {
-    } else if constexpr (ORIG) {
-        float *lut_s = reinterpret_cast<float *>(shared);
-        const f32x4 *lsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0)]);
-        for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s)[i] = lsrc[i];
-        build_quad_table<G, PS>(reinterpret_cast<uint32_t *>(lut_s + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
-        if constexpr (FULL) {
-            const f32x4 *fsrc = reinterpret_cast<const f32x4 *>(P.tab->lut[4 + (raw ? 2 : 0) + 1]);
-            for (int i = threadIdx.x; i < LUT_DWORDS / 4; i += 64 * G::WPB) reinterpret_cast<f32x4 *>(lut_s + OBS_TAB_DWORDS)[i] = fsrc[i];
-            build_quad_table<G, FS>(reinterpret_cast<uint32_t *>(lut_s + OBS_TAB_DWORDS + LUT_DWORDS), threadIdx.x, 64 * G::WPB);
-        }
-    } else {
-        constexpr int NP = tmpl_lds_bytes<G, KIND>(false), NF = FULL ? tmpl_lds_bytes<G, KIND>(true) : 0;
-        const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
-        for (int i = threadIdx.x; i < NP / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared)[i] = tp[i];
-        if constexpr (FULL) {
-            const int4 *tf = reinterpret_cast<const int4 *>(P.tab->tmpl[(raw ? 2 : 0) + 1]);
-            for (int i = threadIdx.x; i < NF / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP)[i] = tf[i];
-        }
-        const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
-        for (int i = threadIdx.x; i < CODETAB_BYTES / 16; i += 64 * G::WPB) reinterpret_cast<int4 *>(shared + NP + NF)[i] = ct[i];
-    }
-    for (int i = threadIdx.x; i < G::S / 4; i += 64 * G::WPB) reinterpret_cast<int *>(obst_s)[i] = reinterpret_cast<const int *>(P.tab->obstacles)[i];
-    for (int i = threadIdx.x; i < COMBAT_BYTES / 4; i += 64 * G::WPB)
-        reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
+    stage_tables<G, KIND>(P, shared, obst_s, threadIdx.x, 64 * G::WPB);
     __syncthreads();   // from here on every wave works on its own game, for all n_steps
     if (env >= P.n_envs) return;
     StepCarry carry{0, 0, 0, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, 0};
@@ -995,7 +907,36 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
 // loaded); also the 'original' channel kinds, which have no steps_kernel
 template <int R_, int C_, int KIND, int VAR = 0>
 __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd<Geo<R_, C_, VAR>, KIND>())) void steps_kernel_pool(const WaveStepsParamsPool SP) {
-    steps_body<R_, C_, KIND, VAR>(SP);
+    using G = Geo<R_, C_, VAR>;
+    static_assert(VAR == 0 || (VAR == 2 && ObsKind<KIND>::NOOBS), "two games per wave: the no-observation kinds only");
+    const SGX_KERNARG WaveStepsParamsPool *top = kernarg_of(SP);
+    const SGX_KERNARG WaveStepsParams *spp = &top->w;
+    const SGX_KERNARG KParams &P = spp->k;
+    __shared__ Lds<G, ObsKind<KIND>::NIB_CH> LW[G::WPB * G::GPW];
+    __shared__ alignas(16) uint8_t shared[shared_table_bytes<G, KIND>()];
+    __shared__ alignas(16) uint8_t obst_s[G::OBST_BYTES + COMBAT_BYTES];
+    const int lane = threadIdx.x & (G::LPG - 1), slot = threadIdx.x / G::LPG;
+    const int64_t env = P.env_first + group_of_block(P) * (G::WPB * G::GPW) + slot;
+    const GameInput in = load_game<G, false>(P, env, lane);
+    stage_tables<G, KIND>(P, shared, obst_s, threadIdx.x, 64 * G::WPB);
+    __syncthreads();   // from here on every wave works on its own game, for all n_steps
+    if (env >= P.n_envs) return;
+    int set = spp->first_set;
+    const int n_steps = spp->n_steps;
+    StepCarryPool carry{};
+    // a handle with a start pool: ONE copy of the step (env_step<PERSIST_ = 3, POOL>) plays the first step and the later ones -- and, with
+    // n_steps = 1, the launches of sgx_step / sgx_rollout's chains: the pool costs one instantiation per observation kind
+    for (int t = 0; t < n_steps; ++t) {
+        const SGX_KERNARG WaveStepsParamsPool *tp = top;
+        int lane_t = lane, slot_t = slot;
+        asm volatile("" : "+s"(tp), "+v"(lane_t), "+v"(slot_t));
+        const SGX_KERNARG WaveStepsParams *sp = &tp->w;
+        if (t && sp->barrier) __builtin_amdgcn_s_barrier();
+        steps_outputs_of(sp, set, carry);
+        carry.first = t == 0;
+        env_step<R_, C_, KIND, false, false, VAR, 3, true>(sp->k, LW[slot_t], shared, obst_s, env, lane_t, in, nullptr, nullptr, &carry, t == n_steps - 1, &tp->pool);
+        set = set + 1 == sp->n_sets ? 0 : set + 1;
+    }
 }
 
 // sgx_step_sync on a handful of games (the N = 1 facade, config 1): latency, not throughput.  ONE game per 512-thread workgroup: wave 0
@@ -1023,18 +964,7 @@ __device__ __forceinline__ void single_body(const KParams &P, uint32_t *__restri
     if (wave == 0) in = load_game<G, false>(P, env, lane);
     const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
     constexpr int NP = tmpl_lds_bytes<G, KIND>(false), NF = FULL ? tmpl_lds_bytes<G, KIND>(true) : 0;
-    {
-        const int4 *tp = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0]);
-        for (int i = tid; i < NP / 16; i += NT) reinterpret_cast<int4 *>(shared)[i] = tp[i];
-        if constexpr (FULL) {
-            const int4 *tf = reinterpret_cast<const int4 *>(P.tab->tmpl[(raw ? 2 : 0) + 1]);
-            for (int i = tid; i < NF / 16; i += NT) reinterpret_cast<int4 *>(shared + NP)[i] = tf[i];
-        }
-        const int4 *ct = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0]);
-        for (int i = tid; i < CODETAB_BYTES / 16; i += NT) reinterpret_cast<int4 *>(shared + NP + NF)[i] = ct[i];
-        for (int i = tid; i < G::S / 4; i += NT) reinterpret_cast<int *>(obst_s)[i] = reinterpret_cast<const int *>(P.tab->obstacles)[i];
-        for (int i = tid; i < COMBAT_BYTES / 4; i += NT) reinterpret_cast<int *>(obst_s + G::OBST_BYTES)[i] = reinterpret_cast<const int *>(P.tab->combat)[i];
-    }
+    stage_tables<G, KIND>(P, shared, obst_s, tid, NT);
     __syncthreads();
     if (wave == 0) env_step<R_, C_, KIND, false, true, 0, 0, POOL>(P, L, shared, obst_s, env, lane, in, nullptr, &so, nullptr, true, pp);
     __syncthreads();

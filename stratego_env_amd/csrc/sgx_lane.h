@@ -1,8 +1,8 @@
 // sgx_lane.h -- lane-per-game logic for boards of at most 16 cells (Micro 3x4, Tiny 4x4): one game per LANE, 64 games per wave
 // Part of libstratego_mi355x.so; included by stratego_mi355x.hip (one translation unit).  The functions in this header are plain
-// scalar code on one game's registers -- no LDS, no cross-lane operation -- and compile for the host as well: tests/lane_harness.cpp
-// builds them with g++ and tests/test_lane_logic_cpu.py plays them against the CPU oracle (test infrastructure only; the product has
-// no CPU path).  The kernel that wraps them (staging, cooperative emission) is in sgx_lane_kernel.h.
+// scalar code on one game's registers -- no LDS, no cross-lane operation -- and compile for the host as well: tests/lane_harness.hip
+// builds them with hipcc --offload-host-only and tests/test_lane_logic_cpu.py plays them against the CPU oracle (test infrastructure
+// only; the product has no CPU path).  The kernels that wrap them (staging, cooperative emission) are in sgx_lane_kernel.h.
 //
 // Why.  With one wave per four 3x4 games (sgx_step.h, Geo::LPG = 16) a step costs 291 VALU instructions per game and a launch of
 // 65,536 Micro games keeps every SIMD's VALU busy for ~31 us: the toy boards ran at the instruction-issue limit, not at the memory
@@ -448,6 +448,88 @@ SGX_HD void lane_store(const LaneGame &g, uint8_t *rec) {
     int32_t *sc = reinterpret_cast<int32_t *>(rec + G::SC_OFF);
     sc[0] = g.turn; sc[1] = g.flags; sc[2] = g.max_turns; sc[3] = g.game_no;
     sc[4] = g.n_events; sc[5] = g.rp0; sc[6] = g.rp1; sc[7] = 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// One step (or, OBSERVE, one observation) of the game in registers: everything between "the game is loaded" and "pack it, render the
+// mask".  Decode, no-op probe, apply, the next mover's moves into V, endings, the mover bit; then the results of game `env`, written
+// at index `renv` (env, or the env's place in a trajectory slot): rewards / dones (maenv:699-805), the auto-reset of a game that
+// ended now -- a sampled setup or, POOL, a record of the start pool --, start_index, player_dev.  `act` = false: a lane without a game
+// (it plays a blank one and writes nothing).  The one composition the step kernels of sgx_lane_kernel.h and the host harness run.
+// ---------------------------------------------------------------------------------------------------------------------
+SGX_HD bool lg_any(bool x) {                               // only a guard against work no lane of the wave needs
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __any(x) != 0;
+#else
+    return x;
+#endif
+}
+struct LanePlayed {
+    int nvalid;                                            // valid moves of the mover the game is left with
+    bool changed;                                          // the action was applied or the game restarted: the record differs
+};
+template <class G, bool OBSERVE, bool POOL, class CombatPtr>
+SGX_HD LanePlayed lane_play(LaneGame &g, uint16_t *ev, uint32_t (&V)[G::K - 1], const KParams &P, const PoolParams *pp, int a_raw, int4 pos_raw,
+                            uint32_t obst_abs, CombatPtr combat, int64_t env, int64_t renv, bool act) {
+    constexpr int K = G::K;
+    const int sflags = P.io.flags;
+    int player = (g.flags & F_PLAYER_M1) ? -1 : 1;
+    const int mover = player;
+    LaneApplied ap{false, false};
+    bool invalid_action = false;
+    if constexpr (!OBSERVE) {
+        const LaneMove m = lane_decode<G>(a_raw, pos_raw, sflags, player);
+        bool has_moves = false;
+        const bool wants_noop = m.valid && m.noop && !(g.flags & F_OVER);
+        if (lg_any(wants_noop)) has_moves = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V) != 0;     // (garbage actions only)
+        ap = lane_apply<G>(g, ev, m, player, obst_abs, combat, P.max_events, sflags, has_moves);
+        if (ap.applied) player = -player; else invalid_action = true;
+    }
+    int nvalid = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, (g.flags & F_OVER) != 0, V);
+    const bool over = lane_finish(g, ap, mover, nvalid);
+    if (over && nvalid != 0) {
+#pragma unroll
+        for (int c = 0; c < K - 1; ++c) V[c] = 0;
+        nvalid = 0;
+    }
+    g.flags = (g.flags & ~F_PLAYER_M1) | (player == -1 ? F_PLAYER_M1 : 0);
+    bool restarted = false;
+    if constexpr (!OBSERVE) {
+        if (act) {                                         // rewards / dones (maenv:699-805)
+            const bool end_invalid = over && (g.flags & F_END_INVALID);
+            float rew_p1 = 0.f, rew_m1 = 0.f;
+            if (over && !end_invalid) {
+                const int w = (g.flags & F_WIN_P1) ? 1 : (g.flags & F_WIN_M1) ? -1 : 0;
+                rew_p1 = w == 0 ? 1e-4f : (float)w;        // impl:838-840
+                rew_m1 = w == 0 ? 1e-4f : (float)-w;
+            }
+            if (P.io.reward_dev) reinterpret_cast<float2 *>(P.io.reward_dev)[renv] = make_float2(rew_p1, rew_m1);
+            if (P.io.done_dev) P.io.done_dev[renv] = over ? 1 : 0;
+            if (P.io.invalid_action_dev) P.io.invalid_action_dev[renv] = invalid_action ? 1 : 0;
+            if (P.io.ending_invalid_dev) P.io.ending_invalid_dev[renv] = end_invalid ? 1 : 0;
+        }
+        if (P.io.auto_reset && ap.applied && over && act) {      // the finished env starts its next game now
+            g.game_no += 1;
+            if constexpr (POOL) {
+                lane_load_start<G>(g, ev, reinterpret_cast<const uint8_t *>(pp->pool), pp->n_pool, pp->pool_flags, P.rec_bytes, P.max_events, P.seed,
+                                   (uint64_t)(P.env_id_offset + env));
+                player = (g.flags & F_PLAYER_M1) ? -1 : 1;
+            } else {
+                lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
+                g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
+                player = 1;
+                for (int i = 0; i < G::EVL_MAX; ++i)
+                    if (i < P.max_events) ev[i] = 0;
+            }
+            nvalid = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V);
+            restarted = true;
+        }
+        if constexpr (POOL)      // the pool index of the env's current game (PoolParams::start_index)
+            if (act && pp->start_index)
+                pp->start_index[renv] = pool_index(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no, pp->n_pool);
+    }
+    if (act && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
+    return LanePlayed{nvalid, act && (ap.applied || restarted)};
 }
 
 }  // namespace

@@ -193,7 +193,43 @@ __device__ __forceinline__ void lane_emit_obs(const uint8_t *rec_base, const int
     wave_sync<G>();
 }
 
-// POOL: the instantiation of a handle with a start pool (sgx_set_start_pool; kernels of their own, like step_kernel_pool)
+// ---- what both step kernels below do around lane_play (sgx_lane.h) ----
+// The workgroup's n_act records are one contiguous span of HBM, env0's first; in LDS every game has an image of its own at `stride`
+// (rec_bytes is 128 or 256: lane_eligible): quad j of the span is the quad at lane_img_off(j).  `img2`: a second buffer that gets the same.
+__device__ __forceinline__ int lane_img_off(const int j, const int rec_bytes) {
+    const int rsh = 31 - __clz(rec_bytes >> 4), gl = j >> rsh;
+    return gl * (rec_bytes + 16) + 16 * (j - (gl << rsh));
+}
+__device__ __forceinline__ void lane_recs_in(const KParams &P, const int64_t env0, const int n_act, uint8_t *img, uint8_t *img2, const int tid, const int nt) {
+    const int4 *src = reinterpret_cast<const int4 *>(P.boards + env0 * (int64_t)P.rec_bytes);
+    for (int j = tid; j < n_act * (P.rec_bytes >> 4); j += nt) {
+        const int4 v = src[j];
+        *reinterpret_cast<int4 *>(img + lane_img_off(j, P.rec_bytes)) = v;
+        if (img2) *reinterpret_cast<int4 *>(img2 + lane_img_off(j, P.rec_bytes)) = v;
+    }
+}
+// the three small tables of the handle into the workgroup's LDS (L: LaneLds / StepsLds)
+template <class LDS>
+__device__ __forceinline__ void lane_stage_tables(LDS &L, const DevTables *tab, const bool raw, const int tid, const int nt) {
+    for (int i = tid; i < (int)sizeof(L.tmpl) / 16; i += nt) reinterpret_cast<int4 *>(L.tmpl)[i] = reinterpret_cast<const int4 *>(tab->tmpl[raw ? 2 : 0])[i];
+    for (int i = tid; i < CODETAB_BYTES / 16; i += nt) reinterpret_cast<int4 *>(L.codetab)[i] = reinterpret_cast<const int4 *>(tab->codetab[raw ? 1 : 0])[i];
+    for (int i = tid; i < COMBAT_BYTES / 16; i += nt) reinterpret_cast<int4 *>(L.combat)[i] = reinterpret_cast<const int4 *>(tab->combat)[i];
+}
+// a lane beyond the launch's last env plays a blank game (it read an unwritten image; its results are never stored)
+__device__ __forceinline__ void lane_blank(LaneGame &g) {
+    g.pc[0] = g.pc[1] = g.po[0] = g.po[1] = 0; g.still[0] = g.still[1] = 0;
+    g.turn = g.flags = g.n_events = g.rp0 = g.rp1 = 0; g.game_no = 0; g.max_turns = 1;
+}
+// the n_act mask rows in `rows` (LDS) are one contiguous span of the mask tensor, 16-byte aligned (env0 is a multiple of 64): 16-byte stores, then the dwords left
+template <class G>
+__device__ __forceinline__ void lane_mask_rows_out(uint8_t *mask, const uint8_t *rows, const int64_t env0, const int n_act, const int lane) {
+    uint8_t *dst = mask + env0 * (int64_t)G::NA;
+    const int n16 = (n_act * G::NA) >> 4, nd = (n_act * G::NA) >> 2;
+    for (int j = lane; j < n16; j += 64) reinterpret_cast<int4 *>(dst)[j] = reinterpret_cast<const int4 *>(rows)[j];
+    if (4 * n16 + lane < nd) reinterpret_cast<uint32_t *>(dst)[4 * n16 + lane] = reinterpret_cast<const uint32_t *>(rows)[4 * n16 + lane];
+}
+
+// POOL: the instantiation of a handle with a start pool (sgx_set_start_pool; kernels of their own, like steps_kernel_pool)
 template <int R_, int C_, bool OBSERVE, bool POOL>
 __device__ __forceinline__ void lane_body(const KParams &P, uint8_t *lane_rec, const PoolParams *pp = nullptr) {
     using G = Geo<R_, C_>;
@@ -208,110 +244,41 @@ __device__ __forceinline__ void lane_body(const KParams &P, uint8_t *lane_rec, c
     const int n_act = (int)((P.n_envs - env0) < 64 ? (P.n_envs - env0) : 64);
     const int64_t env = env0 + lane;
     const bool act = lane < n_act;
-    const int rq = P.rec_bytes >> 4, rsh = 31 - __clz(rq), stride = P.rec_bytes + 16;   // (rec_bytes is 128 or 256: lane_eligible)
-    const int mode = OBSERVE ? 1 : 0;
+    const int stride = P.rec_bytes + 16;
     const int sflags = P.io.flags;
 
     // ---- 1. stage in: records, action, the small tables
-    {
-        const int4 *src = reinterpret_cast<const int4 *>(P.boards + env0 * (int64_t)P.rec_bytes);
-        for (int j = lane; j < n_act * rq; j += 64) {
-            const int gl = j >> rsh, w = j - (gl << rsh);
-            *reinterpret_cast<int4 *>(lane_rec + gl * stride + 16 * w) = src[j];
-        }
-    }
+    lane_recs_in(P, env0, n_act, lane_rec, nullptr, lane, 64);
     int a_raw = 0;
     int4 pos_raw = make_int4(0, 0, 0, 0);
-    if (mode == 0 && act) {
+    if (!OBSERVE && act) {
         if (sflags & SGX_STEP_ACTIONS_POSITIONS) pos_raw = reinterpret_cast<const int4 *>(P.io.actions_dev)[env];
         else a_raw = P.io.actions_dev[env];
     }
     const bool raw = (sflags & SGX_STEP_RAW_OBS) != 0;
-    if (lane < LG::NIBP / 16) reinterpret_cast<int4 *>(L.tmpl)[lane] = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0])[lane];
-    if (lane < CODETAB_BYTES / 16) reinterpret_cast<int4 *>(L.codetab)[lane] = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0])[lane];
-    if (lane < COMBAT_BYTES / 16) reinterpret_cast<int4 *>(L.combat)[lane] = reinterpret_cast<const int4 *>(P.tab->combat)[lane];
+    lane_stage_tables(L, P.tab, raw, lane, 64);
     const uint32_t obst_abs = (uint32_t)__ballot(lane < RC && P.tab->obstacles[lane < RC ? lane : 0] != 0);
     wave_sync<G>();
 
     // ---- 2. play: one game per lane
     uint8_t *myrec = lane_rec + lane * stride;
-    uint16_t *ev = reinterpret_cast<uint16_t *>(myrec + G::EVL_OFF);
     LaneGame g;
-    lane_load<G>(g, myrec);                               // (lanes beyond n_act read their -- unwritten -- image: results unused)
-    if (!act) { g.pc[0] = g.pc[1] = g.po[0] = g.po[1] = 0; g.still[0] = g.still[1] = 0; g.turn = g.flags = g.n_events = g.rp0 = g.rp1 = 0; g.game_no = 0; g.max_turns = 1; }
-    int player = (g.flags & F_PLAYER_M1) ? -1 : 1;
-    const int mover = player;
-    LaneApplied ap{false, false};
-    bool invalid_action = false;
+    lane_load<G>(g, myrec);
+    if (!act) lane_blank(g);
     uint32_t V[K - 1];
-    if (mode == 0) {
-        const LaneMove m = lane_decode<G>(a_raw, pos_raw, sflags, player);
-        bool has_moves = false;
-        const bool wants_noop = m.valid && m.noop && !(g.flags & F_OVER);
-        if (__any(wants_noop)) has_moves = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V) != 0;     // (garbage actions only)
-        ap = lane_apply<G>(g, ev, m, player, obst_abs, L.combat, P.max_events, sflags, has_moves);
-        if (ap.applied) player = -player; else invalid_action = true;
-    }
-    int qi = player == 1 ? 0 : 1;
-    int nvalid = lane_gen_moves<G>(g, qi, obst_abs, (g.flags & F_OVER) != 0, V);
-    const bool over = lane_finish(g, ap, mover, nvalid);
-    if (over && nvalid != 0) {
-#pragma unroll
-        for (int c = 0; c < K - 1; ++c) V[c] = 0;
-        nvalid = 0;
-    }
-    g.flags = (g.flags & ~F_PLAYER_M1) | (player == -1 ? F_PLAYER_M1 : 0);
-    const bool ended_now = ap.applied && over;
-    if (mode == 0 && act) {                               // rewards / dones (maenv:699-805)
-        const bool end_invalid = over && (g.flags & F_END_INVALID);
-        float rew_p1 = 0.f, rew_m1 = 0.f;
-        if (over && !end_invalid) {
-            const int w = (g.flags & F_WIN_P1) ? 1 : (g.flags & F_WIN_M1) ? -1 : 0;
-            rew_p1 = w == 0 ? 1e-4f : (float)w;            // impl:838-840
-            rew_m1 = w == 0 ? 1e-4f : (float)-w;
-        }
-        if (P.io.reward_dev) reinterpret_cast<float2 *>(P.io.reward_dev)[env] = make_float2(rew_p1, rew_m1);
-        if (P.io.done_dev) P.io.done_dev[env] = over ? 1 : 0;
-        if (P.io.invalid_action_dev) P.io.invalid_action_dev[env] = invalid_action ? 1 : 0;
-        if (P.io.ending_invalid_dev) P.io.ending_invalid_dev[env] = end_invalid ? 1 : 0;
-    }
-    bool wrote_reset = false;
-    if (mode == 0 && P.io.auto_reset && ended_now && act) {      // the finished env starts its next game now
-        g.game_no += 1;
-        if constexpr (POOL) {
-            lane_load_start<G>(g, ev, reinterpret_cast<const uint8_t *>(pp->pool), pp->n_pool, pp->pool_flags, P.rec_bytes, P.max_events, P.seed,
-                               (uint64_t)(P.env_id_offset + env));
-            player = (g.flags & F_PLAYER_M1) ? -1 : 1; qi = player == 1 ? 0 : 1;
-            nvalid = lane_gen_moves<G>(g, qi, obst_abs, false, V);
-        } else {
-            lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
-            g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
-            player = 1; qi = 0;
-            for (int i = 0; i < G::EVL_MAX; ++i)
-                if (i < P.max_events) ev[i] = 0;
-            nvalid = lane_gen_moves<G>(g, 0, obst_abs, false, V);
-        }
-        wrote_reset = true;
-    }
-    if constexpr (POOL)      // the pool index of the env's current game (KParams::start_index)
-        if (mode == 0 && act && pp->start_index)
-            pp->start_index[env] = pool_index(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no, pp->n_pool);
-    if (act && P.io.player_dev) P.io.player_dev[env] = (int8_t)player;
-    const bool changed = act && (ap.applied || wrote_reset);
-    if (changed) lane_store<G>(g, myrec);
+    const LanePlayed pl = lane_play<G, OBSERVE, POOL>(g, reinterpret_cast<uint16_t *>(myrec + G::EVL_OFF), V, P, pp, a_raw, pos_raw, obst_abs, L.combat, env, env, act);
+    const int nvalid = pl.nvalid;
+    if (pl.changed) lane_store<G>(g, myrec);
     wave_sync<G>();
 
     // ---- 3. record out (whole records, coalesced)
-    if (__any(changed)) {
+    if (__any(pl.changed)) {
         int4 *dst = reinterpret_cast<int4 *>(P.boards + env0 * (int64_t)P.rec_bytes);
-        for (int j = lane; j < n_act * rq; j += 64) {
-            const int gl = j >> rsh, w = j - (gl << rsh);
-            dst[j] = *reinterpret_cast<const int4 *>(lane_rec + gl * stride + 16 * w);
-        }
+        for (int j = lane; j < n_act * (P.rec_bytes >> 4); j += 64) dst[j] = *reinterpret_cast<const int4 *>(lane_rec + lane_img_off(j, P.rec_bytes));
     }
 
     // ---- 4. mask bytes (and the fused sampler)
-    const bool want_next = mode == 0 && P.io.next_actions_dev != nullptr;
+    const bool want_next = !OBSERVE && P.io.next_actions_dev != nullptr;
     if (P.io.mask_dev || want_next) {
         uint32_t *row = reinterpret_cast<uint32_t *>(L.scratch) + lane * (NA / 4);
         const int total = nvalid == 0 ? 1 : nvalid;
@@ -319,12 +286,7 @@ __device__ __forceinline__ void lane_body(const KParams &P, uint8_t *lane_rec, c
         const int na = lane_emit_mask<G>(V, nvalid == 0, (int)k, [&](int j, uint32_t d) { row[j] = d; });
         if (want_next && act) P.io.next_actions_dev[env] = na;
         wave_sync<G>();
-        if (P.io.mask_dev) {
-            uint8_t *dst = P.io.mask_dev + env0 * (int64_t)NA;                   // 16-byte aligned: env0 is a multiple of 64
-            const int n16 = (n_act * NA) >> 4, nd = (n_act * NA) >> 2;
-            for (int j = lane; j < n16; j += 64) reinterpret_cast<int4 *>(dst)[j] = reinterpret_cast<const int4 *>(L.scratch)[j];
-            if (4 * n16 + lane < nd) reinterpret_cast<uint32_t *>(dst)[4 * n16 + lane] = reinterpret_cast<const uint32_t *>(L.scratch)[4 * n16 + lane];
-        }
+        if (P.io.mask_dev) lane_mask_rows_out<G>(P.io.mask_dev, L.scratch, env0, n_act, lane);
         wave_sync<G>();
     }
 
@@ -410,22 +372,11 @@ __device__ __forceinline__ void lane_steps_body(const StepsParams &SP, uint8_t *
     const int n_act = (int)((P.n_envs - env0) < 64 ? (P.n_envs - env0) : 64);
     const int64_t env = env0 + lane;
     const bool act = lane < n_act;
-    const int rq = P.rec_bytes >> 4, rsh = 31 - __clz(rq), stride = P.rec_bytes + 16, buf_bytes = 64 * stride;
-    const int sflags = P.io.flags;
-    const bool raw = (sflags & SGX_STEP_RAW_OBS) != 0;
+    const int stride = P.rec_bytes + 16, buf_bytes = 64 * stride;
+    const bool raw = (P.io.flags & SGX_STEP_RAW_OBS) != 0;
     // ---- stage in: the 64 records into BOTH buffers (so that every byte of an image is defined whichever buffer goes back to HBM), tables
-    {
-        const int4 *src = reinterpret_cast<const int4 *>(P.boards + env0 * (int64_t)P.rec_bytes);
-        for (int j = tid; j < n_act * rq; j += NT) {
-            const int gl = j >> rsh, w = j - (gl << rsh);
-            const int4 v = src[j];
-            *reinterpret_cast<int4 *>(steps_rec + gl * stride + 16 * w) = v;
-            *reinterpret_cast<int4 *>(steps_rec + buf_bytes + gl * stride + 16 * w) = v;
-        }
-        for (int i = tid; i < LG::NIBP / 16; i += NT) reinterpret_cast<int4 *>(L.tmpl)[i] = reinterpret_cast<const int4 *>(P.tab->tmpl[raw ? 2 : 0])[i];
-        for (int i = tid; i < CODETAB_BYTES / 16; i += NT) reinterpret_cast<int4 *>(L.codetab)[i] = reinterpret_cast<const int4 *>(P.tab->codetab[raw ? 1 : 0])[i];
-        for (int i = tid; i < COMBAT_BYTES / 16; i += NT) reinterpret_cast<int4 *>(L.combat)[i] = reinterpret_cast<const int4 *>(P.tab->combat)[i];
-    }
+    lane_recs_in(P, env0, n_act, steps_rec, steps_rec + buf_bytes, tid, NT);
+    lane_stage_tables(L, P.tab, raw, tid, NT);
     const uint32_t obst_abs = (uint32_t)__ballot(lane < RC && P.tab->obstacles[lane < RC ? lane : 0] != 0);
     __syncthreads();
 
@@ -436,7 +387,7 @@ __device__ __forceinline__ void lane_steps_body(const StepsParams &SP, uint8_t *
 #endif
         LaneGame g;
         lane_load<G>(g, steps_rec + buf_bytes + lane * stride);            // (buffer 1: step 0 writes buffer 0)
-        if (!act) { g.pc[0] = g.pc[1] = g.po[0] = g.po[1] = 0; g.still[0] = g.still[1] = 0; g.turn = g.flags = g.n_events = g.rp0 = g.rp1 = 0; g.game_no = 0; g.max_turns = 1; }
+        if (!act) lane_blank(g);
         int na = act ? P.io.actions_dev[env] : 0;
         uint32_t V[K - 1];
         for (int t = 0; t < SP.n_steps; ++t) {
@@ -448,59 +399,66 @@ __device__ __forceinline__ void lane_steps_body(const StepsParams &SP, uint8_t *
                 for (int i = 0; i < G::EVL_MAX; ++i)
                     if (i < P.max_events) ev[i] = pev[i];
             }
-            int player = (g.flags & F_PLAYER_M1) ? -1 : 1;
-            const int mover = player;
-            bool invalid_action = false;
-            const LaneMove m = lane_decode<G>(na, make_int4(0, 0, 0, 0), sflags, player);
-            bool has_moves = false;
-            const bool wants_noop = m.valid && m.noop && !(g.flags & F_OVER);
-            if (__any(wants_noop)) has_moves = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V) != 0;     // (garbage actions only)
-            const LaneApplied ap = lane_apply<G>(g, ev, m, player, obst_abs, L.combat, P.max_events, sflags, has_moves);
-            if (ap.applied) player = -player; else invalid_action = true;
-            int nvalid = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, (g.flags & F_OVER) != 0, V);
-            const bool over = lane_finish(g, ap, mover, nvalid);
-            if (over && nvalid != 0) {
-#pragma unroll
-                for (int c = 0; c < K - 1; ++c) V[c] = 0;
-                nvalid = 0;
-            }
-            g.flags = (g.flags & ~F_PLAYER_M1) | (player == -1 ? F_PLAYER_M1 : 0);
-            const bool ended_now = ap.applied && over;
             const int set = (SP.first_set + t) % SP.n_sets;
             const int64_t renv = env + (int64_t)set * P.traj_res_envs;     // (sgx_step_traj with per-slot results; else traj_res_envs = 0)
-            if (act) {                                                     // rewards / dones (maenv:699-805)
-                const bool end_invalid = over && (g.flags & F_END_INVALID);
-                float rew_p1 = 0.f, rew_m1 = 0.f;
-                if (over && !end_invalid) {
-                    const int w = (g.flags & F_WIN_P1) ? 1 : (g.flags & F_WIN_M1) ? -1 : 0;
-                    rew_p1 = w == 0 ? 1e-4f : (float)w;                    // impl:838-840
-                    rew_m1 = w == 0 ? 1e-4f : (float)-w;
+            int nvalid;
+            if constexpr (!POOL) nvalid = lane_play<G, false, false>(g, ev, V, P, pp, na, make_int4(0, 0, 0, 0), obst_abs, L.combat, env, renv, act).nvalid;
+            else {
+                // lane_play<G, false, true>, kept as this kernel's own text: through the function -- whole, or as a move half and a results half, with
+                // the flags passed in or the result index made at its point of use -- lane_steps_kernel_pool<4,4> spills 144 bytes for 132
+                const int sflags = P.io.flags;
+                int player = (g.flags & F_PLAYER_M1) ? -1 : 1;
+                const int mover = player;
+                bool invalid_action = false;
+                const LaneMove m = lane_decode<G>(na, make_int4(0, 0, 0, 0), sflags, player);
+                bool has_moves = false;
+                const bool wants_noop = m.valid && m.noop && !(g.flags & F_OVER);
+                if (__any(wants_noop)) has_moves = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V) != 0;     // (garbage actions only)
+                const LaneApplied ap = lane_apply<G>(g, ev, m, player, obst_abs, L.combat, P.max_events, sflags, has_moves);
+                if (ap.applied) player = -player; else invalid_action = true;
+                nvalid = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, (g.flags & F_OVER) != 0, V);
+                const bool over = lane_finish(g, ap, mover, nvalid);
+                if (over && nvalid != 0) {
+#pragma unroll
+                    for (int c = 0; c < K - 1; ++c) V[c] = 0;
+                    nvalid = 0;
                 }
-                if (P.io.reward_dev) reinterpret_cast<float2 *>(P.io.reward_dev)[renv] = make_float2(rew_p1, rew_m1);
-                if (P.io.done_dev) P.io.done_dev[renv] = over ? 1 : 0;
-                if (P.io.invalid_action_dev) P.io.invalid_action_dev[renv] = invalid_action ? 1 : 0;
-                if (P.io.ending_invalid_dev) P.io.ending_invalid_dev[renv] = end_invalid ? 1 : 0;
-            }
-            if (P.io.auto_reset && ended_now && act) {                     // the finished env starts its next game now
-                g.game_no += 1;
-                if constexpr (POOL) {
-                    lane_load_start<G>(g, ev, reinterpret_cast<const uint8_t *>(pp->pool), pp->n_pool, pp->pool_flags, P.rec_bytes, P.max_events, P.seed,
-                                       (uint64_t)(P.env_id_offset + env));
-                    player = (g.flags & F_PLAYER_M1) ? -1 : 1;
-                    nvalid = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V);
-                } else {
-                    lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
-                    g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
-                    player = 1;
-                    for (int i = 0; i < G::EVL_MAX; ++i)
-                        if (i < P.max_events) ev[i] = 0;
-                    nvalid = lane_gen_moves<G>(g, 0, obst_abs, false, V);
+                g.flags = (g.flags & ~F_PLAYER_M1) | (player == -1 ? F_PLAYER_M1 : 0);
+                const bool ended_now = ap.applied && over;
+                if (act) {                                                     // rewards / dones (maenv:699-805)
+                    const bool end_invalid = over && (g.flags & F_END_INVALID);
+                    float rew_p1 = 0.f, rew_m1 = 0.f;
+                    if (over && !end_invalid) {
+                        const int w = (g.flags & F_WIN_P1) ? 1 : (g.flags & F_WIN_M1) ? -1 : 0;
+                        rew_p1 = w == 0 ? 1e-4f : (float)w;                    // impl:838-840
+                        rew_m1 = w == 0 ? 1e-4f : (float)-w;
+                    }
+                    if (P.io.reward_dev) reinterpret_cast<float2 *>(P.io.reward_dev)[renv] = make_float2(rew_p1, rew_m1);
+                    if (P.io.done_dev) P.io.done_dev[renv] = over ? 1 : 0;
+                    if (P.io.invalid_action_dev) P.io.invalid_action_dev[renv] = invalid_action ? 1 : 0;
+                    if (P.io.ending_invalid_dev) P.io.ending_invalid_dev[renv] = end_invalid ? 1 : 0;
                 }
+                if (P.io.auto_reset && ended_now && act) {                     // the finished env starts its next game now
+                    g.game_no += 1;
+                    if constexpr (POOL) {
+                        lane_load_start<G>(g, ev, reinterpret_cast<const uint8_t *>(pp->pool), pp->n_pool, pp->pool_flags, P.rec_bytes, P.max_events, P.seed,
+                                           (uint64_t)(P.env_id_offset + env));
+                        player = (g.flags & F_PLAYER_M1) ? -1 : 1;
+                        nvalid = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst_abs, false, V);
+                    } else {
+                        lane_sample_boards<G>(g, P.setups, P.n_setups, P.usable_rows, P.piece_counts, P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no);
+                        g.turn = 0; g.flags = 0; g.n_events = 0; g.rp0 = g.rp1 = 0;
+                        player = 1;
+                        for (int i = 0; i < G::EVL_MAX; ++i)
+                            if (i < P.max_events) ev[i] = 0;
+                        nvalid = lane_gen_moves<G>(g, 0, obst_abs, false, V);
+                    }
+                }
+                if constexpr (POOL)      // the pool index of the env's current game, in this step's slot
+                    if (act && pp->start_index)
+                        pp->start_index[renv] = pool_index(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no, pp->n_pool);
+                if (act && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
             }
-            if constexpr (POOL)      // the pool index of the env's current game, in this step's slot
-                if (act && pp->start_index)
-                    pp->start_index[renv] = pool_index(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)g.game_no, pp->n_pool);
-            if (act && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
             lane_store<G>(g, myrec);                                       // (always: the emitters read this step's image)
             // mask rows (coalesced out by this wave) and the next action
             {
@@ -510,19 +468,15 @@ __device__ __forceinline__ void lane_steps_body(const StepsParams &SP, uint8_t *
                 na = lane_emit_mask<G>(V, nvalid == 0, (int)k, [&](int j, uint32_t d) { row[j] = d; });
                 if (act && P.traj_act_log) P.traj_act_log[env + (int64_t)set * P.traj_out_envs] = na;
                 wave_sync<G>();
-                if (uint8_t *mset = SP.mask_of(set)) {
-                    uint8_t *dst = mset + env0 * (int64_t)NA;              // 16-byte aligned: env0 is a multiple of 64
-                    const int n16 = (n_act * NA) >> 4, nd = (n_act * NA) >> 2;
-                    for (int j = lane; j < n16; j += 64) reinterpret_cast<int4 *>(dst)[j] = reinterpret_cast<const int4 *>(L.maskrows)[j];
-                    if (4 * n16 + lane < nd) reinterpret_cast<uint32_t *>(dst)[4 * n16 + lane] = reinterpret_cast<const uint32_t *>(L.maskrows)[4 * n16 + lane];
-                }
+                if (uint8_t *mset = SP.mask_of(set)) lane_mask_rows_out<G>(mset, L.maskrows, env0, n_act, lane);
                 wave_sync<G>();
             }
             __syncthreads();                                               // barrier t: image t is complete, and emission t - 1 is over
         }
         // ---- the records and the next action go back to HBM once
         if (act && P.io.next_actions_dev) P.io.next_actions_dev[env] = na;
-        {
+        {   // (rsh of its own, not lane_img_off: through a shared record-out helper lane_steps_kernel<4,4> spilled 152 bytes for 148)
+            const int rq = P.rec_bytes >> 4, rsh = 31 - __clz(rq);
             const uint8_t *last = steps_rec + ((SP.n_steps - 1) & 1) * buf_bytes;
             int4 *dst = reinterpret_cast<int4 *>(P.boards + env0 * (int64_t)P.rec_bytes);
             for (int j = lane; j < n_act * rq; j += 64) {

@@ -960,24 +960,21 @@ static int steps_launch(sgx_env *h, StepsParams &sp, KParams &p, const int32_t *
         if constexpr (lane_geometry<Geo<R, C>>()) {
             const unsigned grid = grid_for(p, 64, w);
             const size_t dyn = 2 * 64 * (size_t)(p.rec_bytes + 16);
-            if (dyn + sizeof(StepsLds<Geo<R, C>>) > 64 * 1024 && !h->multi_step_attr) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(&lane_steps_kernel<R, C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
+            // more than 64 KiB of LDS per workgroup has to be asked for, once per kernel symbol (`done`: the handle's note that it was)
+            auto raise_lds = [&](const void *kernel, int &done) {
+                if (dyn + sizeof(StepsLds<Geo<R, C>>) <= 64 * 1024 || done) return true;
+                if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
                     (void)hipGetLastError();
                     h->no_multi_step = 1;
-                    return;
+                    return false;
                 }
-                h->multi_step_attr = 1;
-            }
+                done = 1;
+                return true;
+            };
+            if (!raise_lds(reinterpret_cast<const void *>(&lane_steps_kernel<R, C>), h->multi_step_attr)) return;
             sp.k = p;
             if (h->pool) {
-                if (dyn + sizeof(StepsLds<Geo<R, C>>) > 64 * 1024 && !h->multi_step_attr_pool) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&lane_steps_kernel_pool<R, C>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) {
-                        (void)hipGetLastError();
-                        h->no_multi_step = 1;
-                        return;
-                    }
-                    h->multi_step_attr_pool = 1;
-                }
+                if (!raise_lds(reinterpret_cast<const void *>(&lane_steps_kernel_pool<R, C>), h->multi_step_attr_pool)) return;
                 lane_steps_kernel_pool<R, C><<<grid, 64 * (1 + KSTEP_EMITTERS), dyn, stream>>>(sp, make_pool_params(h));
             } else
                 lane_steps_kernel<R, C><<<grid, 64 * (1 + KSTEP_EMITTERS), dyn, stream>>>(sp);

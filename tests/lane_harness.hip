@@ -71,50 +71,61 @@ void to_state(const LaneGame &g, const uint16_t *ev, uint32_t obst, int64_t *st)
     }
 }
 
-// One env.step() (mode 0) or observation (mode 1) on `state` / `*player` (both updated), the way the device kernel composes the lane
-// functions.  out_flags: bit 0 invalid action, bit 1 done, bit 2 ending invalid; mask: uint8 [NA] of the next mover; kth: the
-// flat index of the k-th valid action of that mask for k = k_sample; rewards for +1 / -1.  The record round trip (lane_store ->
+// What a call may add to a plain step (lh_play): auto-reset, from sampled setups (piece_counts / usable_rows) or, n_pool > 0, from a start
+// pool of n_pool positions [34,R,C] with their movers, packed into records by lane_store; *start_index receives the pool index.
+struct Restart {
+    int auto_reset, usable_rows, n_pool, pool_flags;
+    const int32_t *piece_counts;
+    uint64_t seed, gid;
+    const int64_t *pool_states;
+    const int32_t *pool_players;
+    int32_t *start_index;
+};
+
+// One env.step() (mode 0) or observation (mode 1) on `state` / `*player` (both updated): lane_play of sgx_lane.h, the function the device
+// kernels call, as game 0 of a host KParams whose result pointers are host scalars.  The game is number 0 of env `gid`.  out_flags: bit 0
+// invalid action, bit 1 done, bit 2 ending invalid; mask: uint8 [NA] of the next mover; kth: the flat index of the k-th valid action of
+// that mask for k = k_sample; rewards for +1 / -1 (mode 1 writes no results, like the kernel).  The record round trip (lane_store ->
 // lane_load on the packed layout) is part of every call.
 template <class G>
 int step(int64_t *state, int *player_io, int action, const int32_t *pos, int step_flags, int mode, int max_events, int k_sample, uint8_t *mask_out,
-         int *nvalid_out, int *kth_out, float *rewards, int *out_flags) {
+         int *nvalid_out, int *kth_out, float *rewards, int *out_flags, const Restart &rs = Restart{}) {
+    constexpr int REC = 256;                                // bytes of a record of a board of at most 16 cells
+    if (rs.n_pool > 16) return -2;
     LaneGame g0;
-    alignas(16) uint8_t rec[512];
+    alignas(16) uint8_t rec[REC], pool[16 * REC];
     memset(rec, 0, sizeof(rec));
+    memset(pool, 0, sizeof(pool));
     uint16_t *ev = reinterpret_cast<uint16_t *>(rec + G::EVL_OFF);
-    uint32_t obst;
+    uint32_t obst, pool_obst;
     from_state<G>(state, *player_io, g0, ev, obst);
     lane_store<G>(g0, rec);
+    for (int j = 0; j < rs.n_pool; ++j) {
+        from_state<G>(rs.pool_states + (size_t)j * 34 * G::RC, rs.pool_players[j], g0, reinterpret_cast<uint16_t *>(pool + j * REC + G::EVL_OFF), pool_obst);
+        lane_store<G>(g0, pool + j * REC);
+    }
     LaneGame g;
     lane_load<G>(g, rec);                                   // through the packed record, as the kernel sees a game
     uint8_t combat[256];
     for (int a = 0; a < 16; ++a)
         for (int d = 0; d < 16; ++d) combat[16 * a + d] = (uint8_t)combat_outcome(a, d);
-    int player = (g.flags & F_PLAYER_M1) ? -1 : 1;
-    const int mover = player;
-    LaneApplied ap{false, false};
-    bool invalid = false;
+    alignas(8) float rew[2] = {0.f, 0.f};
+    uint8_t done = 0, invalid = 0, end_invalid = 0;
+    int8_t player = 0;
+    KParams P;
+    memset(&P, 0, sizeof(P));
+    P.usable_rows = rs.usable_rows; P.rec_bytes = REC; P.max_events = max_events; P.n_envs = 1; P.seed = rs.seed; P.env_id_offset = (int64_t)rs.gid;
+    for (int t = 0; t < 12; ++t) P.piece_counts[t] = rs.piece_counts ? rs.piece_counts[t] : 0;
+    P.io.reward_dev = rew; P.io.done_dev = &done; P.io.invalid_action_dev = &invalid; P.io.ending_invalid_dev = &end_invalid; P.io.player_dev = &player;
+    P.io.auto_reset = rs.auto_reset; P.io.flags = step_flags;
+    const PoolParams PP{reinterpret_cast<const int8_t *>(pool), rs.n_pool, rs.pool_flags, rs.start_index};
+    const int4 p4 = make_int4(pos[0], pos[1], pos[2], pos[3]);
     uint32_t V[G::K - 1];
-    if (mode == 0) {
-        const LaneMove m = lane_decode<G>(action, make_int4(pos[0], pos[1], pos[2], pos[3]), step_flags, player);
-        bool has_moves = false;
-        if (m.valid && m.noop && !(g.flags & F_OVER)) has_moves = lane_gen_moves<G>(g, player == 1 ? 0 : 1, obst, false, V) != 0;
-        ap = lane_apply<G>(g, ev, m, player, obst, combat, max_events, step_flags, has_moves);
-        if (ap.applied) player = -player; else invalid = true;
-    }
-    const int qi = player == 1 ? 0 : 1;
-    int nvalid = lane_gen_moves<G>(g, qi, obst, (g.flags & F_OVER) != 0, V);
-    const bool over = lane_finish(g, ap, mover, nvalid);
-    if (over && nvalid != 0) { for (int c = 0; c < G::K - 1; ++c) V[c] = 0; nvalid = 0; }
-    g.flags = (g.flags & ~F_PLAYER_M1) | (player == -1 ? F_PLAYER_M1 : 0);
-    const bool end_invalid = over && (g.flags & F_END_INVALID);
-    rewards[0] = rewards[1] = 0.f;
-    if (over && !end_invalid) {
-        const int w = (g.flags & F_WIN_P1) ? 1 : (g.flags & F_WIN_M1) ? -1 : 0;
-        rewards[0] = w == 0 ? 1e-4f : (float)w;
-        rewards[1] = w == 0 ? 1e-4f : (float)-w;
-    }
-    *out_flags = (invalid ? 1 : 0) | (over ? 2 : 0) | (end_invalid ? 4 : 0);
+    const int nvalid = mode       ? lane_play<G, true, false>(g, ev, V, P, &PP, action, p4, obst, combat, 0, 0, true).nvalid
+                       : rs.n_pool ? lane_play<G, false, true>(g, ev, V, P, &PP, action, p4, obst, combat, 0, 0, true).nvalid
+                                   : lane_play<G, false, false>(g, ev, V, P, &PP, action, p4, obst, combat, 0, 0, true).nvalid;
+    rewards[0] = rew[0]; rewards[1] = rew[1];
+    *out_flags = (invalid ? 1 : 0) | (done ? 2 : 0) | (end_invalid ? 4 : 0);
     uint32_t *mw = reinterpret_cast<uint32_t *>(mask_out);
     *kth_out = lane_emit_mask<G>(V, nvalid == 0, k_sample, [&](int j, uint32_t d) { mw[j] = d; });
     *nvalid_out = nvalid;
@@ -140,22 +151,29 @@ int sample(const int32_t *piece_counts, int usable_rows, uint64_t seed, uint64_t
 }  // namespace
 
 #define LH_API extern "C" __attribute__((visibility("default")))
-#define LH_GEOMETRIES(X) X(3, 4) X(4, 4) X(4, 3) X(3, 3) X(3, 5)
+// the board sizes the harness is instantiated for: `return CALL;` with G = the board's Geo, -1 for any other size
+#define LH_ON_BOARD(CALL)                                        \
+    if (R == 3 && C == 4) { using G = Geo<3, 4>; return CALL; }  \
+    if (R == 4 && C == 4) { using G = Geo<4, 4>; return CALL; }  \
+    if (R == 4 && C == 3) { using G = Geo<4, 3>; return CALL; }  \
+    return -1
 
 LH_API int lh_step(int R, int C, int64_t *state, int *player_io, int action, const int32_t *pos, int step_flags, int mode, int max_events,
                    int k_sample, uint8_t *mask_out, int *nvalid_out, int *kth_out, float *rewards, int *out_flags) {
-#define LH_CASE(r, c) \
-    if (R == r && C == c) return step<Geo<r, c>>(state, player_io, action, pos, step_flags, mode, max_events, k_sample, mask_out, nvalid_out, kth_out, rewards, out_flags);
-    LH_CASE(3, 4) LH_CASE(4, 4) LH_CASE(4, 3)
-#undef LH_CASE
-    return -1;
+    LH_ON_BOARD(step<G>(state, player_io, action, pos, step_flags, mode, max_events, k_sample, mask_out, nvalid_out, kth_out, rewards, out_flags));
+}
+
+// lh_step (mode 0, spatial actions) with auto-reset: see Restart
+LH_API int lh_play(int R, int C, int64_t *state, int *player_io, int action, int step_flags, int max_events, uint8_t *mask_out, float *rewards, int *out_flags,
+                   int usable_rows, const int32_t *piece_counts, uint64_t seed, uint64_t gid, int n_pool, int pool_flags, const int64_t *pool_states,
+                   const int32_t *pool_players, int32_t *start_index) {
+    const int32_t pos[4] = {0, 0, 0, 0};
+    int nvalid, kth;
+    const Restart rs{1, usable_rows, n_pool, pool_flags, piece_counts, seed, gid, pool_states, pool_players, start_index};
+    LH_ON_BOARD(step<G>(state, player_io, action, pos, step_flags, 0, max_events, 0, mask_out, &nvalid, &kth, rewards, out_flags, rs));
 }
 
 LH_API int lh_sample(int R, int C, const int32_t *piece_counts, int usable_rows, uint64_t seed, uint64_t gid, uint64_t j, int max_turns,
                      uint32_t obst, int64_t *state) {
-#define LH_CASE(r, c) \
-    if (R == r && C == c) return sample<Geo<r, c>>(piece_counts, usable_rows, seed, gid, j, max_turns, obst, state);
-    LH_CASE(3, 4) LH_CASE(4, 4) LH_CASE(4, 3)
-#undef LH_CASE
-    return -1;
+    LH_ON_BOARD(sample<G>(piece_counts, usable_rows, seed, gid, j, max_turns, obst, state));
 }

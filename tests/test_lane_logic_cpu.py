@@ -1,8 +1,9 @@
 """The lane-per-game rules (stratego_env_amd/csrc/sgx_lane.h: one game per GPU lane on boards of at most 16 cells) against the CPU
 oracle, WITHOUT a GPU: tests/lane_harness.hip compiles the very same __host__ __device__ functions for the host
 (hipcc --offload-host-only) and this file plays them step by step beside the oracle -- env.step() with valid and garbage actions,
-the functional 1-D / position actions with and without the oscillation flag, the k-th valid action, fresh random setups.  Test
-infrastructure only: the product never loads the harness."""
+the functional 1-D / position actions with and without the oscillation flag, the k-th valid action, fresh random setups, and the
+auto-reset of a finished game from a sampled setup or a start pool.  The harness calls lane_play, the step function the device kernels
+call: what is played here is the kernels' own composition.  Test infrastructure only: the product never loads the harness."""
 import ctypes as C
 import os
 import shutil
@@ -20,6 +21,7 @@ OUT = os.path.join(ROOT, 'tests', '_build', 'liblane_harness.so')
 DEPS = [SRC] + [os.path.join(ROOT, 'stratego_env_amd', 'csrc', f) for f in ('sgx_lane.h', 'sgx_layout.h')] + [os.path.join(ROOT, 'include', 'stratego_mi355x.h')]
 
 ACTIONS_1D, ALLOW_OSC, ACTIONS_POS = 1, 2, 8
+POOL_RANDOM_FIRST_PLAYER, STREAM_POOL = 1, 4
 
 
 @pytest.fixture(scope='module')
@@ -35,7 +37,28 @@ def lh():
     L.lh_step.restype = C.c_int
     L.lh_sample.restype = C.c_int
     L.lh_sample.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.c_uint32, C.c_void_p]
+    L.lh_play.restype = C.c_int
+    L.lh_play.argtypes = ([C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                           C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p])
     return L
+
+
+def lane_play(L, R, Cc, state, player, action, usable, counts, seed, gid, pool=None, pool_players=None, pool_flags=0, max_events=16):
+    """One step with auto_reset on (lh_play): a game that ends restarts from a sampled setup or, with `pool` (int64 [n,34,R,C] states and
+    int32 [n] movers, contiguous), from the pool.  counts: a ctypes int32 [12].  The harness's game is number 0 of env `gid`: a restart
+    starts game 1."""
+    K = 2 * (R - 1) + 2 * (Cc - 1) + 1
+    st = np.array(state, dtype=np.int64)
+    pl, oflags, start_index = C.c_int(int(player)), C.c_int(0), C.c_int32(-1)
+    mask = np.zeros(R * Cc * K, dtype=np.uint8)
+    rew = (C.c_float * 2)()
+    n_pool = 0 if pool is None else len(pool)
+    rc = L.lh_play(R, Cc, st.ctypes.data, C.addressof(pl), int(action), 0, int(max_events), mask.ctypes.data, C.addressof(rew), C.addressof(oflags), usable,
+                   C.addressof(counts), seed, gid, n_pool, pool_flags, pool.ctypes.data if n_pool else None, pool_players.ctypes.data if n_pool else None,
+                   C.addressof(start_index))
+    assert rc == 0
+    return {'state': st, 'player': pl.value, 'mask': mask.reshape(R, Cc, K), 'rewards': (rew[0], rew[1]), 'invalid': bool(oflags.value & 1),
+            'done': bool(oflags.value & 2), 'ending_invalid': bool(oflags.value & 4), 'start_index': start_index.value}
 
 
 def lane_step(L, R, Cc, state, player, action=0, pos=(0, 0, 0, 0), flags=0, mode=0, max_events=16, k=0):
@@ -223,3 +246,102 @@ def test_fresh_setups_match_the_oracle(lh, name):
         st = np.zeros((34, R, Cc), dtype=np.int64)
         assert lh.lh_sample(R, Cc, pc, usable, seed, g, j, max_turns, obst, st.ctypes.data_as(C.c_void_p)) == 0
         assert np.array_equal(st, orc.reset_state(cv, seed, g, j)), (name, seed, g, j)
+
+
+def _play_with_auto_reset(lh, name, n_games, restart, pool=None, pool_players=None):
+    """`n_games` oracle games from random maps, every step also played by lane_play with auto_reset on.  While the game runs the two
+    agree on everything; at the terminal step the results are the finished game's and restart(got, seed, gid, flags) checks the game the
+    env was given.  Returns the number of terminal steps and of those that ended invalid."""
+    R, Cc, pieces, usable, obstacles, max_turns = CONFIGS[name]
+    counts = (C.c_int32 * 12)(*[pieces.get(t, 0) for t in range(1, 13)])
+    rng = np.random.RandomState(zlib.crc32(name.encode()) % 1000 + 23)
+    env = _oracle_env(R, Cc, pieces, obstacles, max_turns)
+    n_end = n_end_invalid = 0
+    for game in range(n_games):
+        seed, gid, flags = 0xA5 + 977 * game, 31 * game + (2 ** 33 if game % 7 == 0 else 0), POOL_RANDOM_FIRST_PLAYER * (game & 1)
+        j0 = orc.rng_below(orc.rng(seed, gid, 0, STREAM_POOL, 0), len(pool)) if pool is not None else -1
+        mask = env.reset(*_random_maps(rng, R, Cc, pieces, usable, obstacles))[1][env.MASK]
+        for t in range(max_turns + 1):
+            valid = np.flatnonzero(mask.reshape(-1))
+            a = int(valid[rng.randint(len(valid))])
+            got = lane_play(lh, R, Cc, env.state, env.player, a, usable, counts, seed, gid, pool, pool_players, flags)
+            obs, rew, dones, infos = env.step({env.player: a})
+            assert not got['invalid'] and got['done'] == bool(dones['__all__']), (name, game, t)
+            if dones['__all__']:
+                assert got['rewards'] == (np.float32(rew[1]), np.float32(rew[-1])), (name, game, t)
+                assert got['ending_invalid'] == bool(infos[1]['game_result_was_invalid']), (name, game, t)
+                n_end += 1
+                n_end_invalid += int(got['ending_invalid'])
+                restart(got, seed, gid, flags)
+                break
+            mask = obs[env.player][env.MASK]
+            assert np.array_equal(got['state'], env.state) and got['player'] == env.player and got['rewards'] == (0.0, 0.0), (name, game, t)
+            assert np.array_equal(got['mask'], mask.astype(np.uint8)) and not got['ending_invalid'] and got['start_index'] == j0, (name, game, t)
+        else:
+            raise AssertionError("a game outlived max_turns")
+    return n_end, n_end_invalid
+
+
+def _first_mask(name, state, player):
+    R, Cc, pieces, usable, obstacles, max_turns = CONFIGS[name]
+    return _oracle_env(R, Cc, pieces, obstacles, max_turns).reset(initial_state_override=state, first_player_override=player)[player]['valid_actions_mask'].astype(np.uint8)
+
+
+@pytest.mark.parametrize('name', ['micro', 'tiny', 'zoo44'])
+def test_auto_reset_starts_a_sampled_setup(lh, name):
+    """A game that ends with auto_reset on: the step's rewards / done / ending-invalid are the finished game's; the state is the env's
+    game 1 -- the oracle's so_reset_env --, player +1 moves first, and the mask is that fresh game's."""
+    R, Cc, pieces, usable, obstacles, max_turns = CONFIGS[name]
+    cv = orc.make_cvariant(R, Cc, max_turns, obstacles, [pieces.get(t, 0) for t in range(1, 13)], usable)
+
+    def restart(got, seed, gid, flags):
+        fresh = orc.reset_state(cv, seed, gid, 1)
+        assert np.array_equal(got['state'], fresh) and got['player'] == 1, (name, seed, gid)
+        assert np.array_equal(got['mask'], _first_mask(name, fresh, 1)), (name, seed, gid)
+    n_end, n_end_invalid = _play_with_auto_reset(lh, name, 200, restart)
+    assert n_end == 200
+    if name == 'micro':                                    # (20 turns: games end both ways)
+        assert 0 < n_end_invalid < n_end, (n_end, n_end_invalid)
+
+
+@pytest.mark.parametrize('name', ['micro', 'tiny', 'zoo44'])
+def test_auto_reset_starts_from_the_pool(lh, name):
+    """The same with a start pool of five positions from the middle of oracle games, packed into records by lane_store: the new game is
+    record j = rng_below(rng(seed, env, game 1, stream 4, 0), 5) (PoolFollower.start of tests/test_start_pool_cpu.py) -- whole: clock, recent
+    moves and captures come with it --, j is written to start_index, and the mover is the record's or, with SGX_POOL_RANDOM_FIRST_PLAYER (odd
+    games here), the draw's."""
+    R, Cc, pieces, usable, obstacles, max_turns = CONFIGS[name]
+    rng = np.random.RandomState(5)
+    env = _oracle_env(R, Cc, pieces, obstacles, max_turns)
+    pool, players = [], []
+    for _ in range(400):                                   # (bounded) running games with a capture behind them, movers of both colours
+        mask = env.reset(*_random_maps(rng, R, Cc, pieces, usable, obstacles))[1][env.MASK]
+        for t in range(4 + len(pool) % 2 + 2 * int(rng.randint(3))):
+            valid = np.flatnonzero(mask.reshape(-1))
+            obs, _, dones, _ = env.step({env.player: int(valid[rng.randint(len(valid))])})
+            if dones['__all__']:
+                break
+            mask = obs[env.player][env.MASK]
+        else:
+            if env.state[8:32].sum() > 0 and env.state[6:8].any():
+                pool.append(env.state.copy())
+                players.append(env.player)
+        if len(pool) == 5:
+            break
+    assert len(pool) == 5 and set(players) == {1, -1}
+    pool, pool_players = np.ascontiguousarray(np.stack(pool), dtype=np.int64), np.asarray(players, dtype=np.int32)
+    touched, movers = set(), set()
+
+    def restart(got, seed, gid, flags):
+        j = orc.rng_below(orc.rng(seed, gid, 1, STREAM_POOL, 0), len(pool))
+        p = players[j]
+        if flags & POOL_RANDOM_FIRST_PLAYER:
+            p = -1 if orc.rng_below(orc.rng(seed, gid, 1, STREAM_POOL, 1), 2) == 1 else 1
+        assert got['start_index'] == j and got['player'] == p, (name, seed, gid, flags)
+        assert np.array_equal(got['state'], pool[j]), (name, seed, gid, np.argwhere(got['state'] != pool[j])[:5])
+        assert np.array_equal(got['mask'], _first_mask(name, pool[j], p)), (name, seed, gid, flags)
+        touched.add(j)
+        movers.add((flags, p == players[j]))
+    n_end, _ = _play_with_auto_reset(lh, name, 200, restart, pool, pool_players)
+    assert n_end == 200 and len(touched) == len(pool)
+    assert (POOL_RANDOM_FIRST_PLAYER, False) in movers and (POOL_RANDOM_FIRST_PLAYER, True) in movers and (0, False) not in movers

@@ -131,6 +131,7 @@ typedef struct sgx_step_io {
  *   sgx_set_start_index_out   start_index_dev 4
  *   sgx_expand / sgx_copy_envs   src_index_dev, dst_index_dev 4
  *   sgx_determinize              src_index_dev, hidden_dev 4
+ *   sgx_playout                  src_index_dev, reward_dev, length_dev 4; done_dev, ending_invalid_dev, player_dev 1
  *   sgx_mem_probe        ptr_dev 1024;   sgx_store_probe   ptr_dev 16
  * Change note: these rejections are new error returns for pointers that were never legal (the stores they guard were issued unchecked
  * before; only sgx_decode_obs and the compact path refused them); no struct or signature changed, so SGX_ABI_VERSION stays. */
@@ -271,6 +272,7 @@ int sgx_set_steps_barrier(sgx_env *h, int32_t mode);
 #define SGX_LAUNCH_LANE 1        /* one game per lane (boards of at most 16 cells), one launch per step */
 #define SGX_LAUNCH_MULTI_STEP 2  /* one game per lane, all steps of the call in one launch (sgx_set_multi_step) */
 #define SGX_LAUNCH_MULTI_STEP_WAVE 3   /* one wave per game, all steps of the call in one launch: the boards stay in LDS between the steps */
+#define SGX_LAUNCH_PLAYOUT 4     /* sgx_playout: one wave per game, every move of the playout in one launch (set on dst) */
 int sgx_last_launch_kind(const sgx_env *h);
 
 /* Shares of the eight XCDs in a launch of sgx_step / sgx_observe.  Under a saturating write stream the odd XCDs of MI355X drain their
@@ -577,6 +579,38 @@ int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const s
  * would race and is SGX_EINVAL, like an observer outside {-1, 0, 1}, a handle of another variant or a misaligned pointer (4 bytes).
  * No reference counterpart. */
 int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer, uint64_t draw, int32_t *hidden_dev, void *stream);
+
+/* Playouts: every slot of `dst` plays a position of `src` to the end of its game with uniformly random valid moves, in ONE launch, and
+ * reports who won -- what a determinized-MCTS / ISMCTS / PIMC caller does with a sampled world (sgx_determinize) or an expanded node
+ * (sgx_expand).  N = dst's number of envs.  THE RULE (tests/playout_rule.py restates it on the CPU oracle, bit for bit):
+ *   For slot i of dst: g = dst's env_id_offset + i, pos = record src_index[i] of src (i when the index is NULL).
+ *   limit = max(pos.max_turns - pos.turn, 0) + 1, cut to max_steps when max_steps > 0.  (Every applied move advances the turn counter and
+ *   the max-turn ending fires at turn >= max_turns, so no game outlasts the bound: the bound ends the device loop, the game state alone never does.)
+ *   While pos is not over and fewer than `limit` moves have been played: m = the valid-action mask of pos's mover in the mover's perspective
+ *   (what sgx_step writes to mask_dev), n = its number of set entries; the move is the k-th set entry in ascending flat order,
+ *   k = rng_below(rng(dst's seed, g, draw, STREAM_PLAYOUT = 6, turn), max(n, 1)) with the library's counter RNG, turn = pos's turn counter (sgx_get_env_info) -- the
+ *   action of sgx_sample_valid with another RNG word; the move is applied exactly as sgx_step applies it.
+ *   STREAM_PLAYOUT is a stream of its own, so no draw of a rollout, a setup, a pool or a determinization moves; `draw` stands where the
+ *   rollouts' key has the game number, as in sgx_determinize: the same call gives the same games, another draw independent ones.
+ *   Afterwards dst[i] is the final position, whole (a copy of the root where nothing was played); reward / done / ending_invalid / player are
+ *   what a step of sgx_step on that final position reports -- a finished game reports its result on every step: +-1 for a win, the
+ *   reference's tie value, and 0, 0 for a max-turn ending and for a playout that was cut off (done = 0); length = the moves played.
+ * There is no auto-reset, and nothing of src changes unless src == dst.  src == dst with a NULL index works in place (a game's record is
+ * read whole before it is written); with an index it would race like sgx_expand and is SGX_EINVAL.  Also SGX_EINVAL, before anything is
+ * launched: handles of different variants or devices, a NULL index with src smaller than dst, max_steps < 0, flags != 0, a misaligned
+ * pointer (reward_dev, length_dev, src_index_dev 4 bytes; the byte tensors any address), a dst with a start pool set.
+ * Sets dst's sgx_last_launch_kind to SGX_LAUNCH_PLAYOUT.  Added without a change to an existing struct or signature: SGX_ABI_VERSION stays.
+ * Reference counterpart: none -- the loop of examples/basic_game_loop.py:34-63 run to dones['__all__'], as a function of a state. */
+typedef struct sgx_playout_io {
+    float   *reward_dev;          /* [N,2] out (nullable): rewards[+1], rewards[-1] of the FINAL position */
+    uint8_t *done_dev;            /* [N]   out (nullable): 1 = the playout reached the end of its game, 0 = cut off by max_steps */
+    uint8_t *ending_invalid_dev;  /* [N]   out (nullable): the max-turn tie (maenv:777-782) */
+    int8_t  *player_dev;          /* [N]   out (nullable): the mover at the final position */
+    int32_t *length_dev;          /* [N]   out (nullable): moves played, 0 for a root that was already over */
+    int32_t  max_steps;           /* 0 = to the end of the game; > 0 = at most this many moves; < 0 = SGX_EINVAL */
+    int32_t  flags;               /* 0 (anything else SGX_EINVAL) */
+} sgx_playout_io;                 /* 5 pointers + 2 int32 = 48 bytes */
+int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io, uint64_t draw, void *stream);
 
 /* Per-env bookkeeping: int32 [N][4] = {turn count, game number, game_over, current player}. */
 int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream);

@@ -280,7 +280,16 @@ __device__ __forceinline__ auto first_of(const StepCarry *carry) {
     if constexpr (PERSIST_ == 3) return static_cast<const StepCarryPool *>(carry)->first;
     else return std::integral_constant<bool, PERSIST_ != 2>{};
 }
-template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, bool POOL = false, class KP = KParams, class PPT = PoolParams>
+// PLAY (playout_kernel, sgx_playout.h): 0 = none -- every other kernel; 1 = the playout's pass over its ROOT: no move, the record staged, the
+// mover's mask generated and the first action drawn; 2 = one move of the playout.  Both draw the next action with the playout key
+// (pp->draw in the place of game_no, STREAM_PLAYOUT), store nothing -- no per-step result, no next action, no record -- and never auto-reset:
+// the position lives in LDS and *carry until the kernel writes it after its loop.  pp is the playout's PlayParams then.
+template <int PLAY, class KP>
+__device__ __forceinline__ int mode_of(const KP &P) {
+    if constexpr (PLAY != 0) return PLAY == 1 ? 1 : 0;
+    else return P.mode;
+}
+template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, bool POOL = false, class KP = KParams, class PPT = PoolParams, int PLAY = 0>
 __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsKind<KIND>::NIB_CH> &L, const uint8_t *shared, const uint8_t *obst_s,
                                          const int64_t env, const int lane, const GameInput &in, int8_t *rec_out = nullptr, StepOut *so = nullptr,
                                          StepCarry *carry = nullptr, const bool last = true, const PPT *pp = nullptr) {
@@ -297,7 +306,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     STAMP(0);
     // the step's output tensors: the launch's, or -- one of several steps of a multi-step launch -- this step's output set
     float *const io_obs = PERSIST ? carry->obs : P.io.obs_dev, *const io_fobs = PERSIST ? carry->fobs : P.io.fobs_dev;
-    uint8_t *const io_mask = PERSIST ? carry->mask : P.io.mask_dev;
+    uint8_t *const io_mask = PLAY ? nullptr : PERSIST ? carry->mask : P.io.mask_dev;
     // where this step's results go: env, or -- a multi-step launch into a trajectory buffer that keeps every step's results -- the env's
     // place in this step's slot
     int64_t renv = env;
@@ -381,7 +390,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     bool applied = false, invalid_action = false, noop_path = false;
     int mover = player;
 
-    if (P.mode == 0) {
+    if (mode_of<PLAY>(P) == 0) {
         // ------------------------------------------------------------------------------------------
         // decode (maenv:684-689): flat spatial index -> positions -> 1-D index -> absolute 1-D index
         // ------------------------------------------------------------------------------------------
@@ -524,7 +533,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     int qi = player == 1 ? 0 : 1;
     // Launches of the no-observation kind that want neither the mask nor a next action (search expansion, sgx_expand; logic-only steps)
     // only need to know WHETHER the next mover has a move (the opponent-stuck ending): no mask bits, no counts, one cell per ray.
-    const bool want_bits = !NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr);
+    const bool want_bits = PLAY != 0 || !NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr);
 #ifdef SGX_ABLATE
     if (SGX_ABLATED(P.map_arg, 3)) return;                              // staging only
     int nvalid = gen_mask(L, qi, over, lane, P.map_arg);
@@ -556,7 +565,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
         rew_p1 = w == 0 ? 1e-4f : (float)w;     // impl:838-840
         rew_m1 = w == 0 ? 1e-4f : (float)-w;
     }
-    if (P.mode == 0) {
+    if (!PLAY && P.mode == 0) {
         // one store instruction for the rewards (lanes 0/1) and one for the three byte flags (lanes 0..2)
         if (lane < 2 && P.io.reward_dev) P.io.reward_dev[2 * renv + lane] = lane ? rew_m1 : rew_p1;
         uint8_t *fp = lane == 0 ? P.io.done_dev : lane == 1 ? P.io.invalid_action_dev : lane == 2 ? P.io.ending_invalid_dev : nullptr;
@@ -623,7 +632,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
 
     // ---- auto-reset: the finished env starts its next game now
     bool wrote_reset = false;
-    if (P.mode == 0 && ended_now && P.io.auto_reset) {
+    if (!PLAY && P.mode == 0 && ended_now && P.io.auto_reset) {
         game_no += 1;
         if constexpr (POOL) {                  // a position of the start pool, with its own clock, mover, recent moves and captures
             const StartScalars st = load_start_record(L, P, *pp, env, game_no, lane);
@@ -649,7 +658,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
 
     STAMP(4);   // results / terminal handling done
     // ---- outputs for the next mover
-    if (lane == 0 && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
+    if (!PLAY && lane == 0 && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
     if constexpr (SPLIT) {
         if (lane == 0) { so->qi = qi; so->n_events = n_events; so->rp0 = rp0; so->rp1 = rp1; }
     } else {
@@ -685,7 +694,11 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
         if (io_fobs) render(FS{}, true, qi, io_fobs + env * (int64_t)(RC * FS::NCH));
     }
     STAMP(6);   // obs stores issued
-    if (P.mode == 0 && P.io.next_actions_dev) {
+    if constexpr (PLAY != 0) {
+        const int total = nvalid == 0 ? 1 : nvalid;
+        const uint32_t k = rng_below(sgx_rng(P.seed, (uint64_t)(P.env_id_offset + env), pp->draw, STREAM_PLAYOUT, (uint32_t)turn), (uint32_t)total);
+        carry->na = kth_valid(L, (int)k, lane);
+    } else if (P.mode == 0 && P.io.next_actions_dev) {
         const int total = nvalid == 0 ? 1 : nvalid;
         const uint32_t k = rng_below(sgx_rng(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)game_no, STREAM_ACTION, (uint32_t)turn), (uint32_t)total);
         const int na = kth_valid(L, (int)k, lane);

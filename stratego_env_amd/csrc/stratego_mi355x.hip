@@ -81,6 +81,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 #include "sgx_mask.h"
 #include "sgx_setup.h"
 #include "sgx_step.h"
+#include "sgx_playout.h"
 #include "sgx_lane.h"
 #include "sgx_lane_kernel.h"
 #include "sgx_aux_kernels.h"
@@ -2063,6 +2064,47 @@ SGX_API int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index
         dst->boards, src->boards, src_index_dev, hidden_dev, dst->n_envs, dst->seed, dst->env_id_offset, draw, observer, S, dst->sc_off - 2 * sb, sb,
         dst->sc_off, dst->rec_bytes, cells);
     HIP_TRY(hipGetLastError());
+    return SGX_OK;
+}
+
+SGX_API int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io, uint64_t draw, void *stream) {
+    if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_playout: handle or io is NULL%s");
+    if (int rc = same_variant(dst, src)) return rc;
+    if (!src_index_dev && src->n_envs < dst->n_envs) return fail(SGX_EINVAL, "without src_index_dev the source handle needs at least as many envs%s");
+    // wave i reads record src_index[i] while another wave of the same launch writes that record (the identity call is safe: a wave holds
+    // its whole record in LDS before it writes)
+    if (src == dst && src_index_dev)
+        return fail(SGX_EINVAL, "sgx_playout: src == dst with an index array would race; play out into a second handle%s");
+    if (io->max_steps < 0) return fail(SGX_EINVAL, "sgx_playout: max_steps must be 0 (to the end of the game) or the most moves to play%s");
+    if (io->flags != 0) return fail(SGX_EINVAL, "sgx_playout: flags must be 0%s");
+    if (dst->pool) return fail(SGX_EINVAL, "sgx_playout: dst has a start pool set (a playout never restarts a game); clear it or play out into another handle%s");
+    if (int rc = check_aligned("sgx_playout", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_playout", "reward_dev", io->reward_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_playout", "length_dev", io->length_dev, 4)) return rc;
+    SGX_ON_DEVICE(dst->device);
+    PlayoutParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.k = make_params(dst);           // (io all NULL / 0: spatial actions in the mover's perspective, no auto-reset, no per-step output)
+    sp.k.mode = 0;
+    sp.k.src_boards = src->boards;
+    sp.k.src_index = src_index_dev;
+    sp.play.draw = draw;
+    sp.play.reward = io->reward_dev; sp.play.done = io->done_dev; sp.play.ending_invalid = io->ending_invalid_dev;
+    sp.play.player = io->player_dev; sp.play.length = io->length_dev;
+    sp.play.max_steps = io->max_steps;
+    int32_t w[8];
+    launch_setup(dst, sp.k, 1, w);
+    if (int rc = for_geometry(dst, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            with_half_wave<R, C, 8>(dst, [&](auto var) {           // the geometry of the logic-only launches
+                constexpr int VAR = decltype(var)::value;
+                using G = Geo<R, C, VAR>;
+                const unsigned grid = geo_grid<G>(sp.k, w);
+                playout_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
+            });
+        })) return rc;
+    HIP_TRY(hipGetLastError());
+    dst->last_kind = SGX_LAUNCH_PLAYOUT;
     return SGX_OK;
 }
 

@@ -1,0 +1,80 @@
+"""Perfect-information Monte Carlo move choice for B live games at once, on the device: the loop playouts were built for.
+
+    python -m stratego_env_amd.examples.pimc_move_chooser [--version fives] [--games 8] [--worlds 4] [--steps 6]
+
+For every game the mover does not see the opponent's piece types.  PIMC samples W worlds that look the same to the mover
+(PackedStates.determinize), tries every valid root action in every world (PackedStates.expand, whose parent_index fans the worlds out over
+the actions), plays each child to the end with random moves (PackedStates.playout) and picks the action with the best mean result from the
+mover's side.  Three library calls and plain torch around them; nothing leaves the device until the chosen actions do, and the live env
+is only read.
+"""
+import argparse
+
+import torch
+
+from stratego_env_amd.procedural_env import PackedStates
+from stratego_env_amd.vec_env import VecStrategoEnv
+
+
+def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0):
+    """env: a live VecStrategoEnv of B games.  -> (actions int64 [B]: the chosen absolute 1-D action per game, -1 where the game is over;
+    values float32 [B, action_size]: the mean playout result of every valid root action from the root mover's side, -inf elsewhere).
+    The worlds and the playouts are keyed by (seed, slot, draw): the same arguments give the same choice."""
+    B, W, dev = env.num_envs, int(n_worlds), env.device
+    dev_index = dev.index
+    info = env.env_info()
+    mover, live = info[:, 3].to(torch.int8), info[:, 2] == 0
+    # W worlds per game, world-major: slot w * B + b is world w of game b
+    worlds = PackedStates(env.variant, B * W, device=dev_index, seed=seed)
+    children = None
+    try:
+        game_of_world = torch.arange(B, dtype=torch.int32, device=dev).repeat(W)
+        worlds.determinize(env, src_index=game_of_world, observer=0, draw=draw)
+        # the mover's valid actions are the same in every world of a game: world 0 speaks for all
+        mask = worlds.valid_moves_as_1d_mask()[:B] != 0
+        mask &= live[:, None]
+        A = mask.shape[1]
+        values = torch.full((B, A), float('-inf'), dtype=torch.float32, device=dev)
+        game, action = mask.nonzero(as_tuple=True)                    # the M (game, action) pairs to try
+        M = int(game.numel())
+        if M:
+            # child slot w * M + m: action m's move played in world w of its game
+            parent = (torch.arange(W, device=dev)[:, None] * B + game[None, :]).reshape(-1).to(torch.int32)
+            children = PackedStates(env.variant, W * M, device=dev_index, seed=seed)
+            valid, _ = children.expand(worlds, action.repeat(W).to(torch.int32), parent_index=parent)
+            assert bool(valid.all())
+            res = children.playout(children, max_steps=max_steps, draw=draw)          # in place: the children are scratch
+            value = res.value_for(mover[game].repeat(W))
+            sums = torch.zeros(B * A, dtype=torch.float32, device=dev)
+            sums.index_add_(0, (game * A + action).repeat(W), value)
+            values = torch.where(mask, sums.view(B, A) / W, values)
+        actions = torch.where(mask.any(dim=1), values.argmax(dim=1), torch.full((B,), -1, dtype=torch.int64, device=dev))
+        return actions, values
+    finally:
+        worlds.close()
+        if children is not None:
+            children.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--version', default='fives')
+    ap.add_argument('--games', type=int, default=8)
+    ap.add_argument('--worlds', type=int, default=4)
+    ap.add_argument('--steps', type=int, default=6, help='random moves played before the choice')
+    args = ap.parse_args()
+    env = VecStrategoEnv(args.version, args.games, seed=1, auto_reset=False)
+    env.reset()
+    env.rollout_steps(args.steps)
+    actions, values = choose_moves(env, args.worlds)
+    for b, a in enumerate(actions.tolist()):
+        if a < 0:
+            print("game %d: over" % b)
+        else:
+            print("game %d: action %d, mean playout value %+.3f over %d worlds (%d actions tried)"
+                  % (b, a, float(values[b, a]), args.worlds, int(torch.isfinite(values[b]).sum())))
+    env.close()
+
+
+if __name__ == '__main__':
+    main()

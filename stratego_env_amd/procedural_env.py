@@ -409,8 +409,47 @@ class BatchedStrategoProceduralEnv:
         finally:
             src.close()
 
+    def playout(self, states, players, max_steps=0, draw=0, return_states=False):
+        """Every state played to the end of its game with uniformly random valid moves (PackedStates.playout: pack -> playout into a scratch
+        pool -> unpack when asked, for callers on the reference layout).  max_steps: 0 = to the end, else at most that many moves.
+        -> PlayoutResult (reward [n,2], done, ending_invalid, player, length; value_for(player)); with return_states
+        (result, final states int64 [n,34,R,C], their players int8 [n]).  No reference counterpart: the loop of
+        examples/basic_game_loop.py run to dones['__all__'], as a function of a state."""
+        src = self.pack(states, players)
+        try:
+            dst = self.new_packed(src.n)
+            try:
+                res = dst.playout(src, max_steps=max_steps, draw=draw)
+                if not return_states:
+                    return res
+                final, final_players = dst.unpack()
+                return res, final, final_players
+            finally:
+                dst.close()
+        finally:
+            src.close()
+
     def close(self):
         self._vec.close()
+
+
+class PlayoutResult:
+    """What PackedStates.playout reports per slot (device tensors): reward float32 [n,2] = the final position's rewards of players +1 / -1
+    (+-1 for a win, the reference's tie value, 0, 0 for a max-turn ending and for a playout cut off by max_steps), done uint8 (0 = cut off),
+    ending_invalid uint8 (the max-turn tie), player int8 (the mover at the final position), length int32 (moves played)."""
+
+    def __init__(self, reward, done, ending_invalid, player, length):
+        self.reward, self.done, self.ending_invalid, self.player, self.length = reward, done, ending_invalid, player, length
+
+    def value_for(self, player):
+        """The reward column of `player` per slot: +1 / -1 for all, or an int8 tensor [n] of +-1 (a search wants the value from the root
+        mover's side).  -> float32 [n]."""
+        if isinstance(player, int):
+            if player not in (1, -1):
+                raise ValueError("player must be +1 or -1")
+            return self.reward[:, 0 if player == 1 else 1]
+        p = torch.as_tensor(player).to(device=self.reward.device).reshape(-1)
+        return torch.where(p > 0, self.reward[:, 0], self.reward[:, 1])
 
 
 class PackedStates:
@@ -487,6 +526,35 @@ class PackedStates:
                                               int(draw) & 0xFFFFFFFFFFFFFFFF, hidden.data_ptr(), vec._stream()), vec._L)
         vec._next_actions_fresh = False
         return hidden
+
+    def playout(self, src, src_index=None, max_steps=0, draw=0):
+        """Play src[src_index[i]] to the end of its game with uniformly random valid moves, for every slot i of this pool, in one launch
+        (sgx_playout; the rule is in include/stratego_mi355x.h): self[i] becomes the final position, `src` stays what it was.  `src`: a
+        PackedStates (this pool itself for an in-place call without src_index) or a live VecStrategoEnv of the same variant; max_steps: 0 =
+        to the end, else at most that many moves; the moves are keyed by (this pool's seed, its env_id_offset + i, draw, the position's turn),
+        so many slots of one root -- and another `draw` -- play different games.  -> PlayoutResult."""
+        vec = self._vec
+        src_vec = src._vec if isinstance(src, PackedStates) else src
+        if src_vec is vec and src_index is not None:
+            raise ValueError("in-place playouts through src_index would race (a record may be overwritten before it is read): "
+                             "play out into another pool")
+        si = None if src_index is None else torch.as_tensor(src_index).to(device=self.device, dtype=torch.int32).reshape(self.n).contiguous()
+        res = PlayoutResult(torch.empty((self.n, 2), dtype=torch.float32, device=self.device),
+                            torch.empty((self.n,), dtype=torch.uint8, device=self.device),
+                            torch.empty((self.n,), dtype=torch.uint8, device=self.device),
+                            torch.empty((self.n,), dtype=torch.int8, device=self.device),
+                            torch.empty((self.n,), dtype=torch.int32, device=self.device))
+        io = _lib.SgxPlayoutIO(res.reward.data_ptr(), res.done.data_ptr(), res.ending_invalid.data_ptr(), res.player.data_ptr(),
+                               res.length.data_ptr(), int(max_steps), 0)
+        with torch.cuda.device(self.device):
+            _lib.check(vec._L.sgx_playout(vec._h, src_vec._h, None if si is None else si.data_ptr(), io, int(draw) & 0xFFFFFFFFFFFFFFFF,
+                                          vec._stream()), vec._L)
+        vec._next_actions_fresh = False
+        return res
+
+    @property
+    def last_launch_kind(self):
+        return self._vec.last_launch_kind
 
     def valid_moves_as_1d_mask(self):
         out = torch.empty((self.n, self._vec.variant.action_size), dtype=torch.uint8, device=self.device)

@@ -132,6 +132,7 @@ typedef struct sgx_step_io {
  *   sgx_expand / sgx_copy_envs   src_index_dev, dst_index_dev 4
  *   sgx_determinize              src_index_dev, hidden_dev 4
  *   sgx_playout                  src_index_dev, reward_dev, length_dev 4; done_dev, ending_invalid_dev, player_dev 1
+ *   sgx_replay                   src_index_dev, actions_dev, lengths_dev, applied_dev, consumed_dev, reward_dev 4; stop_dev, done_dev, ending_invalid_dev, player_dev 1
  *   sgx_mem_probe        ptr_dev 1024;   sgx_store_probe   ptr_dev 16
  * Change note: these rejections are new error returns for pointers that were never legal (the stores they guard were issued unchecked
  * before; only sgx_decode_obs and the compact path refused them); no struct or signature changed, so SGX_ABI_VERSION stays. */
@@ -273,6 +274,7 @@ int sgx_set_steps_barrier(sgx_env *h, int32_t mode);
 #define SGX_LAUNCH_MULTI_STEP 2  /* one game per lane, all steps of the call in one launch (sgx_set_multi_step) */
 #define SGX_LAUNCH_MULTI_STEP_WAVE 3   /* one wave per game, all steps of the call in one launch: the boards stay in LDS between the steps */
 #define SGX_LAUNCH_PLAYOUT 4     /* sgx_playout: one wave per game, every move of the playout in one launch (set on dst) */
+#define SGX_LAUNCH_REPLAY 5      /* sgx_replay: one wave per game, every entry of the action list in one launch (set on dst) */
 int sgx_last_launch_kind(const sgx_env *h);
 
 /* Shares of the eight XCDs in a launch of sgx_step / sgx_observe.  Under a saturating write stream the odd XCDs of MI355X drain their
@@ -611,6 +613,54 @@ typedef struct sgx_playout_io {
     int32_t  flags;               /* 0 (anything else SGX_EINVAL) */
 } sgx_playout_io;                 /* 5 pointers + 2 int32 = 48 bytes */
 int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io, uint64_t draw, void *stream);
+
+/* Replay: every slot of `dst` becomes a position of `src` advanced by a GIVEN list of actions, all entries in ONE launch -- what a learner
+ * that kept start records and the action log of sgx_step_traj does to get back to (game, t), what a search does to re-derive a node from
+ * its root and the path to it, and how a recorded game is played.  N = dst's number of envs.  THE RULE (tests/replay_rule.py restates it on
+ * the CPU oracle, bit for bit):
+ *   For slot i of dst: pos = record src_index[i] of src (i when the index is NULL); len = lengths_dev[i] clamped to [0, max_len] (max_len
+ *   when lengths_dev is NULL); entry t of the list is actions_dev[i * game_stride + t * step_stride]; c = m = 0.  Then, repeatedly:
+ *     1. c == len: stop = 0, end (the list is exhausted).
+ *     2. pos is over: stop = 1, end.  Entries after the end of the game are not read.
+ *     3. entry c is applied to pos exactly as sgx_step applies an action: the same decode (flat spatial index in the mover's perspective;
+ *        with SGX_REPLAY_ACTIONS_1D an absolute 1-D index as sgx_expand takes it), the same validity checks -- an out-of-range value
+ *        (np.unravel_index raises) and a no-op while the mover has a move are invalid --, the same endings, and no auto-reset.
+ *     4. valid: m++, c++.
+ *     5. invalid with SGX_REPLAY_SKIP_INVALID: c++, pos unchanged.
+ *     6. invalid without it: stop = 2, end; c is not advanced, so entry c is the offending one.
+ *   A count (len <= max_len) bounds the loop; the game state alone never does.
+ *   Afterwards dst[i] is pos, whole (a copy of the root where nothing was applied); reward / done / ending_invalid / player are what a step
+ *   of sgx_step on that final position reports, as sgx_playout reports them (0, 0 and done = 0 for a game that is not over);
+ *   applied = m, consumed = c.
+ * There is no random draw anywhere: the result is a function of (record, list, flags), dst's seed does not enter.  There is no auto-reset,
+ * and nothing of src changes unless src == dst.  src == dst with a NULL index works in place (a game's record is read whole before it is
+ * written); with an index it would race like sgx_expand and is SGX_EINVAL.  Also SGX_EINVAL, before anything is launched: handles of
+ * different variants or devices, a NULL index with src smaller than dst, max_len < 0, unknown flag bits, a negative stride, actions_dev
+ * NULL with max_len > 0, (N - 1) * game_stride + (max_len - 1) * step_stride >= actions_elems, a misaligned pointer (actions_dev,
+ * lengths_dev, applied_dev, consumed_dev, reward_dev, src_index_dev 4 bytes; the byte tensors any address), a dst with a start pool set.
+ * max_len == 0 is legal: a copy, with the roots' own results reported.
+ * Strides are in elements and may be anything >= 0: (L, 1) is a dense game-major [N][L] tensor, (1, slot_envs) the [T][N] action log of
+ * sgx_step_traj (actions_log_dev) as it is; a game's lanes fetch a chunk of consecutive entries per load, so step_stride == 1 reads whole
+ * lines and any other stride one entry per line.
+ * Sets dst's sgx_last_launch_kind to SGX_LAUNCH_REPLAY.  Added without a change to an existing struct or signature: SGX_ABI_VERSION stays.
+ * Reference counterpart: none -- env.step() in a loop over a recorded list (examples/basic_game_loop.py:34-63), as a function of a state. */
+#define SGX_REPLAY_SKIP_INVALID      1   /* an invalid action is passed over (position unchanged) and the replay goes on */
+#define SGX_REPLAY_ACTIONS_1D        2   /* entries are absolute 1-D indices (as sgx_expand's SGX_STEP_ACTIONS_1D); default: flat spatial, mover's perspective (as sgx_step) */
+#define SGX_REPLAY_ALLOW_OSCILLATION 4   /* as SGX_STEP_ALLOW_OSCILLATION */
+typedef struct sgx_replay_io {
+    const int32_t *actions_dev;   /* entry t of slot i: actions_dev[i*game_stride + t*step_stride] */
+    const int32_t *lengths_dev;   /* [N] nullable (= max_len for all); clamped to [0, max_len] */
+    int32_t *applied_dev;         /* [N] out, nullable: moves applied */
+    int32_t *consumed_dev;        /* [N] out, nullable: entries gone past (applied or skipped) */
+    uint8_t *stop_dev;            /* [N] out, nullable: 0 list exhausted, 1 game over, 2 invalid action */
+    float   *reward_dev;          /* [N,2] out, nullable: rewards[+1], rewards[-1] of the FINAL position */
+    uint8_t *done_dev, *ending_invalid_dev;   /* [N] out, nullable */
+    int8_t  *player_dev;          /* [N] out, nullable: the mover at the final position */
+    int64_t game_stride, step_stride;         /* in elements, >= 0: (L,1) dense game-major, (1,slot_envs) the trajectory's [T][N] log */
+    int64_t actions_elems;        /* int32 elements addressable from actions_dev: the host checks the last index against it */
+    int32_t max_len, flags;
+} sgx_replay_io;                  /* 9 pointers + 3 int64 + 2 int32 = 104 bytes */
+int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_replay_io *io, void *stream);
 
 /* Per-env bookkeeping: int32 [N][4] = {turn count, game number, game_over, current player}. */
 int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream);

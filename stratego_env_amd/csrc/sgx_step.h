@@ -284,9 +284,14 @@ __device__ __forceinline__ auto first_of(const StepCarry *carry) {
 // mover's mask generated and the first action drawn; 2 = one move of the playout.  Both draw the next action with the playout key
 // (pp->draw in the place of game_no, STREAM_PLAYOUT), store nothing -- no per-step result, no next action, no record -- and never auto-reset:
 // the position lives in LDS and *carry until the kernel writes it after its loop.  pp is the playout's PlayParams then.
+// 3 / 4 (replay_kernel, sgx_replay.h): the same two passes with a GIVEN action -- 3 stages the root and plays nothing, 4 applies carry->na
+// exactly as a step applies its action.  Neither draws anything nor needs mask bits: like sgx_expand they only ask whether the next mover
+// has a move (gen_any), and pp is unused.  An invalid action leaves the carry's turn counter where it was: every valid action on an
+// unfinished game advances it (the no-op of a mover without a move included) and a finished game is never stepped, so the caller reads
+// validity from the counter and StepCarry keeps its size.
 template <int PLAY, class KP>
 __device__ __forceinline__ int mode_of(const KP &P) {
-    if constexpr (PLAY != 0) return PLAY == 1 ? 1 : 0;
+    if constexpr (PLAY != 0) return (PLAY == 1 || PLAY == 3) ? 1 : 0;
     else return P.mode;
 }
 template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, bool POOL = false, class KP = KParams, class PPT = PoolParams, int PLAY = 0>
@@ -533,7 +538,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     int qi = player == 1 ? 0 : 1;
     // Launches of the no-observation kind that want neither the mask nor a next action (search expansion, sgx_expand; logic-only steps)
     // only need to know WHETHER the next mover has a move (the opponent-stuck ending): no mask bits, no counts, one cell per ray.
-    const bool want_bits = PLAY != 0 || !NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr);
+    const bool want_bits = PLAY < 3 && (PLAY != 0 || !NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr));
 #ifdef SGX_ABLATE
     if (SGX_ABLATED(P.map_arg, 3)) return;                              // staging only
     int nvalid = gen_mask(L, qi, over, lane, P.map_arg);
@@ -694,11 +699,11 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
         if (io_fobs) render(FS{}, true, qi, io_fobs + env * (int64_t)(RC * FS::NCH));
     }
     STAMP(6);   // obs stores issued
-    if constexpr (PLAY != 0) {
+    if constexpr (PLAY == 1 || PLAY == 2) {
         const int total = nvalid == 0 ? 1 : nvalid;
         const uint32_t k = rng_below(sgx_rng(P.seed, (uint64_t)(P.env_id_offset + env), pp->draw, STREAM_PLAYOUT, (uint32_t)turn), (uint32_t)total);
         carry->na = kth_valid(L, (int)k, lane);
-    } else if (P.mode == 0 && P.io.next_actions_dev) {
+    } else if (PLAY == 0 && P.mode == 0 && P.io.next_actions_dev) {
         const int total = nvalid == 0 ? 1 : nvalid;
         const uint32_t k = rng_below(sgx_rng(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)game_no, STREAM_ACTION, (uint32_t)turn), (uint32_t)total);
         const int na = kth_valid(L, (int)k, lane);

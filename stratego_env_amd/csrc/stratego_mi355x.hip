@@ -82,6 +82,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 #include "sgx_setup.h"
 #include "sgx_step.h"
 #include "sgx_playout.h"
+#include "sgx_replay.h"
 #include "sgx_lane.h"
 #include "sgx_lane_kernel.h"
 #include "sgx_aux_kernels.h"
@@ -2105,6 +2106,64 @@ SGX_API int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev
         })) return rc;
     HIP_TRY(hipGetLastError());
     dst->last_kind = SGX_LAUNCH_PLAYOUT;
+    return SGX_OK;
+}
+
+SGX_API int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_replay_io *io, void *stream) {
+    if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_replay: handle or io is NULL%s");
+    if (dst->device != src->device) return fail(SGX_EINVAL, "sgx_replay: the two handles live on different devices%s");
+    if (memcmp(&dst->cfg, &src->cfg, sizeof(sgx_config)) != 0 || dst->rec_bytes != src->rec_bytes)
+        return fail(SGX_EINVAL, "sgx_replay: the two handles were created for different variants%s");
+    if (!src_index_dev && src->n_envs < dst->n_envs) return fail(SGX_EINVAL, "sgx_replay: without src_index_dev the source handle needs at least as many envs%s");
+    // wave i reads record src_index[i] while another wave of the same launch writes that record (the identity call is safe: a wave holds
+    // its whole record in LDS before it writes)
+    if (src == dst && src_index_dev)
+        return fail(SGX_EINVAL, "sgx_replay: src == dst with an index array would race; replay into a second handle%s");
+    if (io->max_len < 0) return fail(SGX_EINVAL, "sgx_replay: max_len must not be negative%s");
+    if (io->flags & ~(SGX_REPLAY_SKIP_INVALID | SGX_REPLAY_ACTIONS_1D | SGX_REPLAY_ALLOW_OSCILLATION)) return fail(SGX_EINVAL, "sgx_replay: unknown flag bits%s");
+    if (io->game_stride < 0 || io->step_stride < 0) return fail(SGX_EINVAL, "sgx_replay: game_stride and step_stride must not be negative%s");
+    if (io->max_len > 0) {
+        if (!io->actions_dev) return fail(SGX_EINVAL, "sgx_replay: actions_dev is NULL with max_len > 0%s");
+        // the last index the kernel may read, (N - 1) * game_stride + (max_len - 1) * step_stride, against what the caller says is addressable
+        // (128-bit arithmetic: two int64 products)
+        const __int128 last = (__int128)(dst->n_envs - 1) * io->game_stride + (__int128)(io->max_len - 1) * io->step_stride;
+        if (last >= (__int128)io->actions_elems)
+            return fail(SGX_EINVAL, "sgx_replay: (N - 1) * game_stride + (max_len - 1) * step_stride reaches past actions_elems%s");
+    }
+    if (dst->pool) return fail(SGX_EINVAL, "sgx_replay: dst has a start pool set (a replay never restarts a game); clear it or replay into another handle%s");
+    if (int rc = check_aligned("sgx_replay", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_replay", "actions_dev", io->actions_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_replay", "lengths_dev", io->lengths_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_replay", "applied_dev", io->applied_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_replay", "consumed_dev", io->consumed_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_replay", "reward_dev", io->reward_dev, 4)) return rc;
+    SGX_ON_DEVICE(dst->device);
+    ReplayParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.k = make_params(dst);           // (io all NULL / 0: no auto-reset, no per-step output; the decode flags follow)
+    sp.k.mode = 0;
+    sp.k.src_boards = src->boards;
+    sp.k.src_index = src_index_dev;
+    sp.k.io.flags = ((io->flags & SGX_REPLAY_ACTIONS_1D) ? SGX_STEP_ACTIONS_1D : 0) | ((io->flags & SGX_REPLAY_ALLOW_OSCILLATION) ? SGX_STEP_ALLOW_OSCILLATION : 0);
+    sp.rep.actions = io->actions_dev; sp.rep.lengths = io->lengths_dev;
+    sp.rep.applied = io->applied_dev; sp.rep.consumed = io->consumed_dev; sp.rep.stop = io->stop_dev;
+    sp.rep.reward = io->reward_dev; sp.rep.done = io->done_dev; sp.rep.ending_invalid = io->ending_invalid_dev; sp.rep.player = io->player_dev;
+    sp.rep.game_stride = io->game_stride; sp.rep.step_stride = io->step_stride;
+    sp.rep.max_len = io->max_len;
+    sp.rep.skip_invalid = (io->flags & SGX_REPLAY_SKIP_INVALID) ? 1 : 0;
+    int32_t w[8];
+    launch_setup(dst, sp.k, 1, w);
+    if (int rc = for_geometry(dst, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            with_half_wave<R, C, 8>(dst, [&](auto var) {           // the geometry of the logic-only launches
+                constexpr int VAR = decltype(var)::value;
+                using G = Geo<R, C, VAR>;
+                const unsigned grid = geo_grid<G>(sp.k, w);
+                replay_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
+            });
+        })) return rc;
+    HIP_TRY(hipGetLastError());
+    dst->last_kind = SGX_LAUNCH_REPLAY;
     return SGX_OK;
 }
 

@@ -429,6 +429,27 @@ class BatchedStrategoProceduralEnv:
         finally:
             src.close()
 
+    def replay(self, states, players, actions, lengths=None, skip_invalid=False, actions_1d=True, allow_piece_oscillation=False, return_states=True):
+        """Every state advanced by its list of actions, all moves in one launch (PackedStates.replay: pack -> replay into a scratch pool ->
+        unpack, for callers on the reference layout).  actions: int32 [n, L]; absolute 1-D indices as get_next_state takes them
+        (actions_1d=False: flat spatial indices in the mover's perspective); lengths: int32 [n] (None: L for all).
+        -> (ReplayResult, states int64 [n,34,R,C], players int8 [n]); with return_states=False the ReplayResult alone.  The same as L calls
+        of get_next_state that stop at the end of the game and -- unless skip_invalid -- at the first invalid action."""
+        src = self.pack(states, players)
+        try:
+            dst = self.new_packed(src.n)
+            try:
+                res = dst.replay(src, actions, lengths=lengths, skip_invalid=skip_invalid, actions_1d=actions_1d,
+                                 allow_piece_oscillation=allow_piece_oscillation)
+                if not return_states:
+                    return res
+                final, final_players = dst.unpack()
+                return res, final, final_players
+            finally:
+                dst.close()
+        finally:
+            src.close()
+
     def close(self):
         self._vec.close()
 
@@ -452,6 +473,18 @@ class PlayoutResult:
         return torch.where(p > 0, self.reward[:, 0], self.reward[:, 1])
 
 
+class ReplayResult:
+    """What replay reports per slot (device tensors): applied int32 (moves applied), consumed int32 (entries gone past, applied or
+    skipped), stop uint8 (0 = the list was exhausted, 1 = the game was over, 2 = an invalid action: entry `consumed` is the offending one),
+    and, of the final position as for a playout, reward float32 [n,2], done uint8, ending_invalid uint8, player int8."""
+
+    def __init__(self, applied, consumed, stop, reward, done, ending_invalid, player):
+        self.applied, self.consumed, self.stop = applied, consumed, stop
+        self.reward, self.done, self.ending_invalid, self.player = reward, done, ending_invalid, player
+
+    value_for = PlayoutResult.value_for
+
+
 class PackedStates:
     """A pool of n game states in the library's packed records (0.5 KB each for Barrage against 27 KB in the reference's int64
     layout), for tree-search callers of get_next_state (penv:148-155): nodes are expanded pool-to-pool with `expand`, copied with
@@ -469,16 +502,18 @@ class PackedStates:
         return self._vec.export_state()
 
     def copy_from(self, src, src_index=None, dst_index=None, n=None):
-        """records src[src_index[i]] -> self[dst_index[i]] (index tensors int32 on the device, None = identity)."""
+        """records src[src_index[i]] -> self[dst_index[i]] (index tensors int32 on the device, None = identity).  `src`: a PackedStates or a
+        live VecStrategoEnv of the same variant (a snapshot of start records)."""
         vec = self._vec
-        if src is self and (src_index is not None or dst_index is not None):
+        src_vec = src._vec if isinstance(src, PackedStates) else src
+        if src_vec is vec and (src_index is not None or dst_index is not None):
             raise ValueError("an indexed copy inside one pool would race (records read and rewritten by one launch): copy into another pool")
         si = None if src_index is None else torch.as_tensor(src_index).to(device=self.device, dtype=torch.int32).contiguous()
         di = None if dst_index is None else torch.as_tensor(dst_index).to(device=self.device, dtype=torch.int32).contiguous()
         if n is None:
-            n = si.numel() if si is not None else di.numel() if di is not None else min(self.n, src.n)
+            n = si.numel() if si is not None else di.numel() if di is not None else min(self.n, src_vec.num_envs)
         with torch.cuda.device(self.device):
-            _lib.check(vec._L.sgx_copy_envs(vec._h, None if di is None else di.data_ptr(), src._vec._h,
+            _lib.check(vec._L.sgx_copy_envs(vec._h, None if di is None else di.data_ptr(), src_vec._h,
                                             None if si is None else si.data_ptr(), int(n), vec._stream()), vec._L)
         return self
 
@@ -551,6 +586,17 @@ class PackedStates:
                                           vec._stream()), vec._L)
         vec._next_actions_fresh = False
         return res
+
+    def replay(self, src, actions, lengths=None, src_index=None, skip_invalid=False, actions_1d=False, allow_piece_oscillation=False):
+        """self[i] = src[src_index[i]] advanced by the list actions[i, :lengths[i]], every move in one launch (sgx_replay; the rule is in
+        include/stratego_mi355x.h); `src` stays what it was.  `src`: a PackedStates (this pool itself for an in-place call without
+        src_index) or a live VecStrategoEnv of the same variant.  actions: int32 device tensor [n, L] with any non-negative strides, taken
+        as it is (the transposed [T, N] action log of a trajectory needs no copy); lengths int32 [n] (None: L for all).  skip_invalid: an
+        invalid entry is passed over, else it ends the replay (stop == 2); actions_1d: absolute 1-D indices as `expand` takes them, else
+        flat spatial indices in the mover's perspective as env.step() takes them.  -> ReplayResult.  (VecStrategoEnv.replay is the same
+        call with a live env as the destination.)"""
+        return self._vec.replay(src, actions, lengths=lengths, src_index=src_index, skip_invalid=skip_invalid, actions_1d=actions_1d,
+                                allow_piece_oscillation=allow_piece_oscillation)
 
     @property
     def last_launch_kind(self):

@@ -787,6 +787,50 @@ class VecStrategoEnv:
         self._next_actions_fresh = False
         return self.observe()
 
+    def replay(self, src, actions, lengths=None, src_index=None, skip_invalid=False, actions_1d=False, allow_piece_oscillation=False):
+        """Every game i of this env becomes src[src_index[i]] advanced by its list actions[i, :lengths[i]], all moves in one launch
+        (sgx_replay; the rule is in include/stratego_mi355x.h); `src` stays what it was.  A following observe() renders the replayed
+        positions' observations and masks: with start records and recorded actions a learner re-renders any (game, t) it samples instead
+        of keeping every step's observation.
+        src: a PackedStates, a snapshot() or another VecStrategoEnv of the same variant (this env itself for an in-place call without
+        src_index).  actions: int32 device tensor [n, L] with ANY non-negative strides, passed through as they are -- traj['actions'][:T].T
+        is taken without a copy.  lengths: int32 [n] (None: L for all).  skip_invalid: an invalid entry is passed over instead of ending
+        the replay; actions_1d: entries are absolute 1-D indices (get_next_state's) instead of flat spatial indices in the mover's
+        perspective.  No auto-reset: a replay stops at the end of its game.  -> ReplayResult."""
+        from .procedural_env import ReplayResult
+        n, dev = self.num_envs, self.device
+        src_vec = getattr(src, '_vec', src)
+        if src_vec is self and src_index is not None:
+            raise ValueError("an in-place replay through src_index would race (a record may be overwritten before it is read): "
+                             "replay into another pool")
+        a = actions
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.int32 or a.device != dev:
+            a = torch.as_tensor(a).to(device=dev, dtype=torch.int32)
+        if a.dim() != 2 or a.shape[0] != n:
+            raise ValueError("actions must be an int32 tensor [%d, L]" % n)
+        L = int(a.shape[1])
+        game_stride, step_stride = (int(x) for x in a.stride())
+        if n * L == 0:
+            game_stride = step_stride = 0
+        if game_stride < 0 or step_stride < 0:
+            raise ValueError("actions must have non-negative strides")
+        elems = a.untyped_storage().nbytes() // 4 - int(a.storage_offset())          # what the view can address from its first element
+        ln = None if lengths is None else torch.as_tensor(lengths).to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+        si = None if src_index is None else torch.as_tensor(src_index).to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+        res = ReplayResult(torch.empty((n,), dtype=torch.int32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev),
+                           torch.empty((n,), dtype=torch.uint8, device=dev), torch.empty((n, 2), dtype=torch.float32, device=dev),
+                           torch.empty((n,), dtype=torch.uint8, device=dev), torch.empty((n,), dtype=torch.uint8, device=dev),
+                           torch.empty((n,), dtype=torch.int8, device=dev))
+        flags = ((_lib.REPLAY_SKIP_INVALID if skip_invalid else 0) | (_lib.REPLAY_ACTIONS_1D if actions_1d else 0)
+                 | (_lib.REPLAY_ALLOW_OSCILLATION if allow_piece_oscillation else 0))
+        io = _lib.SgxReplayIO(a.data_ptr() if L else None, _ptr(ln), res.applied.data_ptr(), res.consumed.data_ptr(), res.stop.data_ptr(),
+                              res.reward.data_ptr(), res.done.data_ptr(), res.ending_invalid.data_ptr(), res.player.data_ptr(),
+                              game_stride, step_stride, elems, L, flags)
+        with torch.cuda.device(dev):
+            _lib.check(self._L.sgx_replay(self._h, src_vec._h, _ptr(si), C.byref(io), self._stream()), self._L)
+        self._next_actions_fresh = False
+        return res
+
     def sample_valid_actions(self, mask=None, out=None):
         """Uniformly random valid action per env from `mask` (default: the current one) -- maenv:830-834."""
         own = mask is None or mask is self.mask

@@ -1,0 +1,557 @@
+"""sgx_replay / PackedStates.replay / VecStrategoEnv.replay on the GPU: the golden games recorded from the reference in one launch per variant
+(skip mode and stop mode), bit for bit the numpy restatement of the rule on the oracle (tests/replay_rule.py, which tests/test_replay_cpu.py
+holds against the golden games) on ragged inputs that cross the kernel's prefetch chunks in both layouts, the in-place call, the per-step
+kernel as a second witness, replay + observe(), NULL outputs and guard bands, the refusals (all host-side), the int64 API and the example.
+
+Every slot of every launch is compared.  The restated moves of a test stay under about 60,000."""
+
+import numpy as np
+import pytest
+
+from tests import replay_rule as rr
+from tests.helpers import load_games
+from tests.test_gpu_playout import CASES, GAMES_PER_WORKGROUP, N_SRC, _np, _roots
+
+pytestmark = pytest.mark.gpu
+
+SGX_EINVAL = -1
+MASK = 'valid_actions_mask'
+GOLDEN = ['barrage', 'standard', 'micro', 'tiny', 'fives', 'medium', 'octa_barrage', 'short_barrage', 'short_standard', 'standard2']
+GOLDEN_WITH_INVALID = GOLDEN[2:]
+# lanes per game of the logic-only launches (Geo::LPG: 16 on boards of up to 16 cells, 32 up to 32 cells and on the two-games-per-wave
+# variant of the boards up to 128 cells, else 64): the size of the kernel's prefetch chunk
+LPG = {'micro': 16, 'tiny': 16, 'fives': 32, 'medium': 32, 'octa_barrage': 32, 'short_barrage': 32, 'barrage': 32, 'standard2': 64}
+
+
+def _results(res):
+    return {'applied': _np(res.applied), 'consumed': _np(res.consumed), 'stop': _np(res.stop), 'reward': _np(res.reward),
+            'done': _np(res.done), 'ending_invalid': _np(res.ending_invalid), 'player': _np(res.player)}
+
+
+def _golden(name):
+    """-> (g, actions int32 [n, longest] padded with -1, lengths int32 [n], errors per game)"""
+    g = load_games(name)
+    off = g['offsets']
+    n = len(off) - 1
+    lengths = (off[1:] - off[:-1]).astype(np.int32)
+    acts = np.full((n, int(lengths.max())), -1, dtype=np.int32)
+    errs = []
+    for gi in range(n):
+        acts[gi, :lengths[gi]] = g['actions'][off[gi]:off[gi + 1]]
+        errs.append(g['errors'][off[gi]:off[gi + 1]].astype(bool))
+    return g, acts, lengths, errs
+
+
+def _golden_roots(name, g):
+    import torch
+    from stratego_env_amd.vec_env import VecStrategoEnv
+    n = len(g['offsets']) - 1
+    env = VecStrategoEnv(name, n, seed=1, auto_reset=False, human_inits=False, placement='plain')
+    env.reset(torch.from_numpy(g['p1_maps'][:n]), torch.from_numpy(g['p2_maps'][:n]))
+    return env
+
+
+# ---- A: the golden games, one launch per variant, skip mode ---------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', GOLDEN)
+def test_golden_games_in_one_launch(name):
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    g, acts, lengths, errs = _golden(name)
+    n = len(lengths)
+    env = _golden_roots(name, g)
+    pool = PackedStates(name, n)
+    res = pool.replay(env, torch.from_numpy(acts).cuda(), lengths=torch.from_numpy(lengths).cuda(), skip_invalid=True)
+    assert pool.last_launch_kind == _lib.LAUNCH_REPLAY
+    got = _results(res)
+    n_err = np.asarray([int(e.sum()) for e in errs], dtype=np.int32)
+    print(name, 'games', n, 'moves', int(lengths.sum()), 'invalid', int(n_err.sum()))
+    assert np.array_equal(got['consumed'], lengths), "consumed == len exactly (more: a read past a list)"
+    assert np.array_equal(got['applied'], lengths - n_err)
+    assert np.array_equal(got['stop'], np.zeros(n, dtype=np.uint8))
+    st, pl = pool.unpack()
+    assert np.array_equal(_np(st), g['final_states'][:n].astype(np.int64))
+    finished = g['finished'][:n].astype(bool)
+    assert np.array_equal(got['done'], finished.astype(np.uint8))
+    assert np.array_equal(got['ending_invalid'][finished], g['ending_invalid'][:n][finished].astype(np.uint8))
+    want_reward = np.zeros((n, 2), dtype=np.float32)
+    want_player = np.empty(n, dtype=np.int8)
+    for gi in range(n):
+        valid = np.flatnonzero(~errs[gi])
+        last = int(g['offsets'][gi]) + int(valid[-1]) if len(valid) else None
+        if finished[gi]:
+            want_reward[gi] = g['rewards'][last]
+        want_player[gi] = 1 if last is None else g['players'][last]
+    assert got['reward'].tobytes() == want_reward.tobytes()
+    assert np.array_equal(got['player'], want_player) and np.array_equal(_np(pl), want_player)
+    pool.close(); env.close()
+
+
+# ---- B: the same fixtures in stop mode, against the rule on the CPU ----------------------------------------------------------------------
+@pytest.mark.parametrize('name', GOLDEN_WITH_INVALID)
+def test_golden_games_stop_at_their_first_invalid_entry(name):
+    import torch
+    from stratego_env_amd.procedural_env import PackedStates
+    g, acts, lengths, errs = _golden(name)
+    n = len(lengths)
+    env = _golden_roots(name, g)
+    states, players = (_np(t) for t in env.export_state())
+    pool = PackedStates(name, n)
+    res = pool.replay(env, torch.from_numpy(acts).cuda(), lengths=torch.from_numpy(lengths).cuda())
+    got = _results(res)
+    first = np.asarray([int(np.flatnonzero(e)[0]) if e.any() else len(e) for e in errs], dtype=np.int32)
+    assert np.array_equal(got['consumed'], first) and np.array_equal(got['applied'], first)
+    assert np.array_equal(got['stop'], np.asarray([2 if e.any() else 0 for e in errs], dtype=np.uint8))
+    assert (got['stop'] == 2).any()
+    _compare(name, pool, res, states, players, acts, lengths, None, dict(skip_invalid=False), (name, 'stop mode'))
+    pool.close(); env.close()
+
+
+def _compare(variant, pool, res, states, players, acts, lengths, index, flags, where, want=None):
+    """the pool's records and the seven result tensors against the restatement; -> the restatement's outputs"""
+    if want is None:
+        want = rr.replay_batch(variant, states, players, acts, lengths, index, **flags)
+    want_s, want_p, want_r, want_d, want_e, want_m, want_c, want_stop = want
+    got = _results(res)
+    assert np.array_equal(got['consumed'], want_c), (where, got['consumed'].tolist(), want_c.tolist())
+    assert np.array_equal(got['applied'], want_m), where
+    assert np.array_equal(got['stop'], want_stop), where
+    assert got['reward'].tobytes() == want_r.tobytes(), where
+    assert np.array_equal(got['done'], want_d) and np.array_equal(got['ending_invalid'], want_e), where
+    assert np.array_equal(got['player'], want_p), where
+    got_s, got_p = pool.unpack()
+    assert np.array_equal(_np(got_s), want_s), where
+    assert np.array_equal(_np(got_p), want_p), where
+    return want
+
+
+# ---- C: ragged inputs against the rule ---------------------------------------------------------------------------------------------------------
+def _make_list(name, state, player, length, rs, inject):
+    """A list of `length` entries from a position: random valid moves played forward by the oracle; `inject`: one entry is invalid instead
+    (-1, the number of spatial actions, or an in-range move the mask refuses) and the position stays; after the end of the game the list
+    goes on with arbitrary in-range entries.  -> (flat spatial entries in the mover's perspective, the same list as absolute 1-D indices)"""
+    env = rr._env(name)
+    ru = env.rules
+    NA, AS = env.rows * env.columns * env.K, ru.action_size
+    obs = env.reset(initial_state_override=np.asarray(state, dtype=np.int64), first_player_override=int(player))
+    sp, d1 = [], []
+    inj_at = int(rs.randint(length)) if (inject and length > 0) else -1
+    for t in range(length):
+        if ru.get_game_ended(env.state, 1) != 0:
+            sp.append(int(rs.randint(NA))); d1.append(int(rs.randint(AS)))
+            continue
+        mask = np.asarray(obs[env.player][MASK]).reshape(-1)
+        if t == inj_at:
+            kind = int(rs.randint(3))
+            if kind == 0:
+                sp.append(-1); d1.append(-1)
+            elif kind == 1:
+                sp.append(NA); d1.append(AS)
+            else:
+                zeros = np.flatnonzero(mask == 0)
+                sp.append(int(zeros[rs.randint(len(zeros))]))
+                zeros1 = np.flatnonzero(ru.get_valid_moves_as_1d_mask(env.state, env.player) == 0)
+                d1.append(int(zeros1[rs.randint(len(zeros1))]))
+            continue
+        valid = np.flatnonzero(mask)
+        a = int(valid[rs.randint(len(valid))])
+        spatial = tuple(int(x) for x in np.unravel_index(a, (env.rows, env.columns, env.K)))
+        sp.append(a)
+        d1.append(ru.get_action_1d_index_from_player_perspective(ru.get_action_1d_index_from_spatial_index(spatial), env.player))
+        obs, _, _, _ = env.step({env.player: a})
+    return sp, d1
+
+
+def _ragged_lists(name, states, players, idx, rs):
+    """-> (spatial int32 [n, L], 1-D int32 [n, L], lengths int32 [n]); the padding holds a valid-looking 0"""
+    lpg = LPG[name]
+    choices = (0, 1, lpg - 1, lpg, lpg + 1, 2 * lpg + 3)
+    n = len(idx)
+    lengths = np.asarray([choices[(i + int(rs.randint(2))) % 6] for i in range(n)], dtype=np.int32)
+    L = 2 * lpg + 3
+    sp = np.zeros((n, L), dtype=np.int32)
+    d1 = np.zeros((n, L), dtype=np.int32)
+    for i, s in enumerate(idx):
+        a, b = _make_list(name, states[s], players[s], int(lengths[i]), rs, inject=(i % 3 == 1))
+        sp[i, :lengths[i]], d1[i, :lengths[i]] = a, b
+    return sp, d1, lengths
+
+
+def _layouts(acts, torch):
+    """the list tensor in two layouts: dense game-major with a game stride beyond the longest list, and the transposed view of [L, n]"""
+    n, L = acts.shape
+    wide = torch.full((n, L + 5), -7, dtype=torch.int32, device='cuda')
+    wide[:, :L] = torch.from_numpy(acts).cuda()
+    dense = wide[:, :L]
+    assert dense.stride() == (L + 5, 1)
+    tn = torch.from_numpy(np.ascontiguousarray(acts.T)).cuda()
+    transposed = tn.T
+    assert transposed.stride() == (1, n) and tuple(transposed.shape) == (n, L)
+    return (('dense', dense, wide), ('transposed', transposed, tn))
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_bit_exact_against_the_rule_on_ragged_lists(name):
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    steps, _, shared = CASES[name]
+    env, states, players, finished = _roots(name, steps)
+    assert finished.any() and not finished.all(), "both finished and unfinished roots"
+    assert not finished[shared]
+    before_t = env.export_state()
+    rs = np.random.RandomState(7)
+    n = 61
+    idx = rs.randint(0, N_SRC, size=n).astype(np.int32)
+    idx[:20] = shared
+    gathered, identity = PackedStates(name, n, seed=3), PackedStates(name, N_SRC, seed=4)
+    moves, stops, wave_mates_differ, shared_differ = 0, set(), False, False
+    for pool, index in ((gathered, idx), (identity, None)):
+        sp, d1, lengths = _ragged_lists(name, states, players, idx if index is not None else np.arange(N_SRC), rs)
+        index_t = None if index is None else torch.from_numpy(index).cuda()
+        lengths_t = torch.from_numpy(lengths).cuda()
+        modes = [(sp, dict(skip_invalid=False)), (sp, dict(skip_invalid=True))]
+        if name == 'fives':
+            modes += [(d1, dict(skip_invalid=False, actions_1d=True)), (d1, dict(skip_invalid=True, actions_1d=True))]
+        for acts, flags in modes:
+            want = None
+            for layout, view, whole in _layouts(acts, torch):
+                keep = whole.clone()
+                res = pool.replay(env, view, lengths=lengths_t, src_index=index_t, **flags)
+                assert pool.last_launch_kind == _lib.LAUNCH_REPLAY
+                where = (name, 'gathered' if index is not None else 'identity', layout, sorted(flags.items()))
+                want = _compare(name, pool, res, states, players, acts, lengths, index, flags, where, want)
+                assert torch.equal(whole, keep), "the action tensor is only read"
+            want_c, want_stop = want[6], want[7]
+            moves += int(want_c.sum())
+            if not flags['skip_invalid'] and 'actions_1d' not in flags:
+                stops |= set(want_stop.tolist())
+            wave_mates_differ |= bool((want_c[0:-1:2] != want_c[1::2]).any())
+            if index is not None:
+                shared_differ |= len(set(want_c[:20].tolist())) >= 2
+    after_t = env.export_state()
+    assert torch.equal(after_t[0], before_t[0]) and torch.equal(after_t[1], before_t[1])           # src untouched
+    assert stops == {0, 1, 2}, "all three stop codes occur"
+    assert wave_mates_differ, "two games that share a wave (slots 2j, 2j + 1) stopped at different counts"
+    assert shared_differ, "the 20 slots of one root went different ways"
+    print(name, 'restated entries', moves)
+    assert moves < 60000
+    gathered.close(); identity.close(); env.close()
+
+
+# ---- D: in place ---------------------------------------------------------------------------------------------------------------------------
+def test_the_in_place_call_equals_pool_to_pool():
+    import torch
+    from stratego_env_amd.procedural_env import PackedStates
+    name = 'fives'
+    env, states, players, finished = _roots(name, CASES[name][0])
+    rs = np.random.RandomState(11)
+    sp, _, lengths = _ragged_lists(name, states, players, np.arange(N_SRC), rs)
+    acts_t, lengths_t = torch.from_numpy(sp).cuda(), torch.from_numpy(lengths).cuda()
+    src, dst = PackedStates(name, N_SRC), PackedStates(name, N_SRC)
+    for skip in (False, True):
+        src.copy_from(env)                                               # (a live env as the source of a copy)
+        assert np.array_equal(_np(src.unpack()[0]), states)
+        res = dst.replay(src, acts_t, lengths=lengths_t, skip_invalid=skip)
+        want = _compare(name, dst, res, states, players, sp, lengths, None, dict(skip_invalid=skip), (name, 'pool to pool', skip))
+        pool_r = _results(res)
+        assert np.array_equal(_np(src.unpack()[0]), states)              # src is only read
+        res2 = src.replay(src, acts_t, lengths=lengths_t, skip_invalid=skip)
+        _compare(name, src, res2, states, players, sp, lengths, None, dict(skip_invalid=skip), (name, 'in place', skip), want)
+        for k, v in _results(res2).items():
+            assert v.tobytes() == pool_r[k].tobytes(), k
+    with pytest.raises(ValueError):
+        src.replay(src, acts_t, src_index=torch.zeros(N_SRC, dtype=torch.int32, device='cuda'))
+    for x in (src, dst, env):
+        x.close()
+
+
+# ---- E: against the per-step kernel, no oracle ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['fives', 'barrage'])
+def test_replay_of_recorded_steps_equals_the_stepped_env(name):
+    import torch
+    from stratego_env_amd.procedural_env import PackedStates
+    from stratego_env_amd.vec_env import VecStrategoEnv
+    T = 70
+    N = 2 * {'fives': GAMES_PER_WORKGROUP['fives'], 'barrage': GAMES_PER_WORKGROUP['short_barrage']}[name] + 3
+    env = VecStrategoEnv(name, N, seed=21, auto_reset=False, human_inits=False, placement='plain')
+    env.reset()
+    start, dst = PackedStates(name, N), PackedStates(name, N)
+    start.copy_from(env)
+    rec = torch.empty((T, N), dtype=torch.int32, device='cuda')
+    for t in range(T):
+        # (a finished game gets an out-of-range entry: flagged invalid and untouched by the step, never read by the replay)
+        over = env.env_info()[:, 2] != 0
+        drawn = env.sample_valid_actions()
+        rec[t] = torch.where(over, torch.full_like(drawn, -1), drawn)
+        env.step(rec[t])
+        assert torch.equal(env.invalid_action != 0, over)
+    res = dst.replay(start, rec.T)                                       # the [T, N] log as it is: strides (1, N)
+    want_s, want_p = env.export_state()
+    got_s, got_p = dst.unpack()
+    assert torch.equal(got_s, want_s) and torch.equal(got_p, want_p)
+    info = env.env_info()
+    assert torch.equal(res.done, (info[:, 2] != 0).to(torch.uint8))
+    assert torch.equal(res.applied, info[:, 0]) and torch.equal(res.applied, res.consumed)      # (the turn counter started at 0)
+    assert not bool((res.stop == 2).any())
+    assert torch.equal(res.stop == 1, res.consumed < T)
+    assert torch.equal(res.reward, env.reward) and torch.equal(res.player, env.player)
+    for x in (start, dst, env):
+        x.close()
+
+
+# ---- F: replay into a live env, then observe() ---------------------------------------------------------------------------------------------
+def test_env_replay_then_observe_renders_the_stepped_position():
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    from stratego_env_amd.vec_env import VecStrategoEnv
+    name, N, T = 'barrage', 8, 20
+    env = VecStrategoEnv(name, N, seed=5, auto_reset=False, human_inits=False, placement='plain')
+    env.reset()
+    start = PackedStates(name, N)
+    start.copy_from(env)
+    rec = torch.empty((T, N), dtype=torch.int32, device='cuda')
+    for t in range(T):
+        # (Barrage scouts reach a flag within a few moves now and then: a finished game gets an out-of-range entry, which leaves it untouched)
+        over = env.env_info()[:, 2] != 0
+        drawn = env.sample_valid_actions()
+        rec[t] = torch.where(over, torch.full_like(drawn, -1), drawn)
+        env.step(rec[t])
+    other = VecStrategoEnv(name, N, seed=99, auto_reset=False, human_inits=False, placement='plain')
+    other.reset()
+    res = other.replay(start, rec.T)
+    assert other.last_launch_kind == _lib.LAUNCH_REPLAY
+    info = env.env_info()
+    assert torch.equal(res.applied, info[:, 0]) and bool((res.stop != 2).all()) and bool((res.applied == T).any())
+    assert torch.equal(other.export_state()[0], env.export_state()[0])
+    obs, mask, player = other.observe()
+    assert obs.cpu().numpy().tobytes() == env.obs.cpu().numpy().tobytes()
+    assert mask.cpu().numpy().tobytes() == env.mask.cpu().numpy().tobytes()
+    assert torch.equal(player, env.player)
+    for x in (start, other, env):
+        x.close()
+
+
+# ---- G: NULL outputs and guard bands ---------------------------------------------------------------------------------------------------------
+OUT_SPECS = (('applied', 1, 'int32'), ('consumed', 1, 'int32'), ('stop', 1, 'uint8'), ('reward', 2, 'float32'), ('done', 1, 'uint8'),
+             ('ending_invalid', 1, 'uint8'), ('player', 1, 'int8'))
+
+
+def test_null_outputs_and_guard_bands():
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    from tests.test_gpu_guard_bands import Arena
+    name, n = 'fives', 37
+    env, states, players, finished = _roots(name, CASES[name][0], n=n)
+    rs = np.random.RandomState(2)
+    sp, _, lengths = _ragged_lists(name, states, players, np.arange(n), rs)
+    Lmax = sp.shape[1]
+    pool = PackedStates(name, n, seed=2, env_id_offset=7)
+    vec = pool._vec
+    L = vec._L
+    want = dict(zip(('state', 'player', 'reward', 'done', 'ending_invalid', 'applied', 'consumed', 'stop'),
+                    rr.replay_batch(name, states, players, sp, lengths, None, skip_invalid=True)))
+    dtypes = {'float32': torch.float32, 'uint8': torch.uint8, 'int8': torch.int8, 'int32': torch.int32}
+
+    def arenas(byte_phase, word_phase):
+        ar = {k: Arena(k, (n, w) if w > 1 else (n,), dtypes[t], word_phase if t in ('float32', 'int32') else byte_phase, vec.device)
+              for k, w, t in OUT_SPECS}
+        ins = {'actions': Arena('actions', (n, Lmax), torch.int32, word_phase, vec.device), 'lengths': Arena('lengths', (n,), torch.int32, word_phase, vec.device)}
+        ins['actions'].t.copy_(torch.from_numpy(sp))
+        ins['lengths'].t.copy_(torch.from_numpy(lengths))
+        return ar, ins
+
+    def call(ptrs, ins):
+        io = _lib.SgxReplayIO(ins['actions'].t.data_ptr(), ins['lengths'].t.data_ptr(), ptrs['applied'], ptrs['consumed'], ptrs['stop'], ptrs['reward'],
+                              ptrs['done'], ptrs['ending_invalid'], ptrs['player'], Lmax, 1, n * Lmax, Lmax, _lib.REPLAY_SKIP_INVALID)
+        return L.sgx_replay(vec._h, env._h, None, io, vec._stream())
+
+    def check_inputs(ins):
+        for a in ins.values():
+            a.check_guards('sgx_replay')
+        assert np.array_equal(ins['actions'].host(), sp) and np.array_equal(ins['lengths'].host(), lengths)
+
+    # the tensors between guard bands, at every phase the contract allows
+    for byte_phase, word_phase in ((0, 0), (1, 4), (3, 12), (13, 0)):
+        ar, ins = arenas(byte_phase, word_phase)
+        assert call({k: a.t.data_ptr() for k, a in ar.items()}, ins) == 0, L.sgx_last_error()
+        torch.cuda.synchronize()
+        check_inputs(ins)
+        for k, a in ar.items():
+            a.check_guards('sgx_replay')
+            a.check_written('sgx_replay')
+            assert a.host().tobytes() == want[k].tobytes(), (k, byte_phase, word_phase)
+        assert np.array_equal(_np(pool.unpack()[0]), want['state'])
+    # each result pointer NULL in turn: the others are still right
+    for skip in [k for k, _, _ in OUT_SPECS]:
+        ar, ins = arenas(0, 0)
+        assert call({k: (None if k == skip else a.t.data_ptr()) for k, a in ar.items()}, ins) == 0, L.sgx_last_error()
+        torch.cuda.synchronize()
+        check_inputs(ins)
+        for k, a in ar.items():
+            a.check_guards('sgx_replay')
+            if k == skip:
+                a.check_untouched('sgx_replay')
+            else:
+                assert a.host().tobytes() == want[k].tobytes(), (k, 'without', skip)
+        assert np.array_equal(_np(pool.unpack()[0]), want['state'])
+    # lengths NULL: every list is max_len long
+    ar, ins = arenas(0, 0)
+    io = _lib.SgxReplayIO(ins['actions'].t.data_ptr(), None, ar['applied'].t.data_ptr(), ar['consumed'].t.data_ptr(), ar['stop'].t.data_ptr(), None, None, None, None,
+                          Lmax, 1, n * Lmax, 5, _lib.REPLAY_SKIP_INVALID)
+    assert L.sgx_replay(vec._h, env._h, None, io, vec._stream()) == 0, L.sgx_last_error()
+    torch.cuda.synchronize()
+    want5 = rr.replay_batch(name, states, players, sp[:, :5], None, None, skip_invalid=True)
+    assert np.array_equal(ar['consumed'].host(), want5[6]) and np.array_equal(ar['applied'].host(), want5[5]) and np.array_equal(ar['stop'].host(), want5[7])
+    assert np.array_equal(_np(pool.unpack()[0]), want5[0])
+    pool.close(); env.close()
+
+
+# ---- H: refusals -------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_are_host_side():
+    """Every refusal is SGX_EINVAL with a message that names sgx_replay; dst, src and the outputs keep what they held."""
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    from tests.test_gpu_playout import _pool_from
+    name, n, Lmax = 'barrage', 16, 6
+    env, states, players, _ = _roots(name, 30, n=n)
+    a, b = _pool_from(env, name, n), _pool_from(env, name, n)
+    foreign = PackedStates('standard', n)
+    small = PackedStates(name, n // 2)
+    L = a._vec._L
+    stream = a._vec._stream()
+    idx = torch.zeros(n + 1, dtype=torch.int32, device='cuda')
+    acts = torch.zeros((n, Lmax + 1), dtype=torch.int32, device='cuda')
+    lens = torch.full((n + 1,), Lmax, dtype=torch.int32, device='cuda')
+    outs = {'applied': torch.full((n + 1,), 77, dtype=torch.int32, device='cuda'), 'consumed': torch.full((n + 1,), 77, dtype=torch.int32, device='cuda'),
+            'stop': torch.full((n,), 77, dtype=torch.uint8, device='cuda'), 'reward': torch.full((n + 1, 2), 77.0, device='cuda'),
+            'done': torch.full((n,), 77, dtype=torch.uint8, device='cuda'), 'ending_invalid': torch.full((n,), 77, dtype=torch.uint8, device='cuda'),
+            'player': torch.full((n,), 77, dtype=torch.int8, device='cuda')}
+
+    def io(max_len=Lmax, flags=0, game_stride=Lmax, step_stride=1, elems=n * Lmax, actions=True, off=None):
+        off = off or {}
+        p = {k: t.data_ptr() + off.get(k, 0) for k, t in outs.items()}
+        return _lib.SgxReplayIO((acts.data_ptr() + off.get('actions', 0)) if actions else None, lens.data_ptr() + off.get('lengths', 0), p['applied'], p['consumed'],
+                                p['stop'], p['reward'], p['done'], p['ending_invalid'], p['player'], game_stride, step_stride, elems, max_len, flags)
+
+    def refused(rc, *words):
+        assert rc == SGX_EINVAL
+        msg = L.sgx_last_error().decode()
+        assert all(w in msg for w in ('sgx_replay',) + words), msg
+
+    ah, bh = a._vec._h, b._vec._h
+    refused(L.sgx_replay(ah, foreign._vec._h, None, io(), stream), 'different variants')
+    with pytest.raises(_lib.SgxError):
+        a.replay(foreign, acts[:, :Lmax])
+    refused(L.sgx_replay(ah, small._vec._h, None, io(), stream), 'at least as many envs')
+    refused(L.sgx_replay(ah, ah, idx.data_ptr(), io(), stream), 'race')
+    with pytest.raises(ValueError):
+        a.replay(a, acts[:, :Lmax], src_index=idx[:n])
+    refused(L.sgx_replay(ah, bh, None, io(max_len=-1), stream), 'max_len')
+    for flags in (8, 16, 1 | 32, -1):
+        refused(L.sgx_replay(ah, bh, None, io(flags=flags), stream), 'flag')
+    refused(L.sgx_replay(ah, bh, None, io(game_stride=-1), stream), 'stride')
+    refused(L.sgx_replay(ah, bh, None, io(step_stride=-1), stream), 'stride')
+    refused(L.sgx_replay(ah, bh, None, io(actions=False), stream), 'actions_dev', 'NULL')
+    refused(L.sgx_replay(ah, bh, None, io(elems=n * Lmax - 1), stream), 'actions_elems')
+    refused(L.sgx_replay(ah, bh, None, io(game_stride=Lmax + 1), stream), 'actions_elems')
+    refused(L.sgx_replay(ah, bh, None, io(game_stride=1 << 62, step_stride=1 << 62, elems=(1 << 63) - 1), stream), 'actions_elems')     # (no wrap-around)
+    for k in ('actions', 'lengths', 'applied', 'consumed', 'reward'):
+        for phase in (1, 2, 3):
+            refused(L.sgx_replay(ah, bh, None, io(off={k: phase}), stream), '%s_dev' % k, '4-byte aligned')
+    refused(L.sgx_replay(ah, bh, idx.data_ptr() + 2, io(), stream), 'src_index_dev', '4-byte aligned')
+    refused(L.sgx_replay(None, bh, None, io(), stream), 'NULL')
+    refused(L.sgx_replay(ah, bh, None, None, stream), 'NULL')
+    # a dst with a start pool set
+    fresh = _pool_from(None, name, n)
+    assert L.sgx_set_start_pool(ah, fresh._vec._h, n, 0) == 0, L.sgx_last_error()
+    refused(L.sgx_replay(ah, bh, None, io(), stream), 'start pool')
+    assert L.sgx_set_start_pool(ah, None, 0, 0) == 0
+    torch.cuda.synchronize()
+    for k, t in outs.items():
+        assert bool((t == 77).all()), k                                    # nothing ran
+    for pool in (a, b):
+        got_s, got_p = pool.unpack()
+        assert np.array_equal(_np(got_s), states) and np.array_equal(_np(got_p), players)
+    # max_len == 0 is a copy, with the roots' own results (and needs no action tensor)
+    fresh_states = _np(fresh.unpack()[0])
+    assert L.sgx_replay(ah, fresh._vec._h, None, io(max_len=0, actions=False, elems=0), stream) == 0, L.sgx_last_error()
+    torch.cuda.synchronize()
+    assert np.array_equal(_np(a.unpack()[0]), fresh_states)
+    assert bool((outs['consumed'][:n] == 0).all()) and bool((outs['applied'][:n] == 0).all()) and bool((outs['stop'] == 0).all())
+    assert bool((outs['done'] == 0).all()) and bool((outs['reward'][:n] == 0).all()) and bool((outs['player'] == 1).all())
+    res = a.replay(b, acts[:, :0])
+    assert np.array_equal(_np(a.unpack()[0]), states) and bool((res.consumed == 0).all())
+    assert np.array_equal(_np(res.player), players)
+    for x in (a, b, foreign, small, fresh, env):
+        x.close()
+
+
+# ---- I: the int64 API ----------------------------------------------------------------------------------------------------------------------
+def test_the_int64_api_equals_get_next_state():
+    import torch
+    from stratego_env_amd.procedural_env import BatchedStrategoProceduralEnv
+    name, n, T = 'fives', 16, 5
+    env, states, players, finished = _roots(name, 4, n=n)
+    assert not finished.any()
+    pe = BatchedStrategoProceduralEnv(name, n)
+    st, pl = torch.from_numpy(states).cuda(), torch.from_numpy(players).cuda()
+    rs = np.random.RandomState(1)
+    acts = np.zeros((n, T), dtype=np.int32)
+    cur, cur_pl = st, pl
+    for t in range(T):
+        mask = _np(pe.get_valid_moves_as_1d_mask(cur, cur_pl))
+        for i in range(n):
+            valid = np.flatnonzero(mask[i])
+            acts[i, t] = valid[rs.randint(len(valid))]
+        cur, cur_pl, ok = pe.get_next_state(cur, cur_pl, torch.from_numpy(acts[:, t]).cuda())
+        assert bool(torch.as_tensor(ok).all())
+    res, final, final_players = pe.replay(st, pl, torch.from_numpy(acts).cuda())
+    assert final.dtype == torch.int64 and torch.equal(final, cur) and torch.equal(final_players.to(cur_pl.dtype), cur_pl)
+    applied = _np(res.applied)
+    assert ((applied == T) | (_np(res.stop) == 1)).all() and (applied > 0).all()
+    only = pe.replay(st, pl, torch.from_numpy(acts).cuda(), return_states=False)
+    assert torch.equal(only.applied, res.applied) and torch.equal(only.value_for(1), res.reward[:, 0])
+    pe.close(); env.close()
+
+
+# ---- the oscillation flag: the two-square position of tests/test_oracle_golden.py, whose seventh move the rule refuses unless allowed ----------
+def test_allow_piece_oscillation_reaches_the_step():
+    import torch
+    from oracle import oracle as orc
+    from stratego_env_amd.procedural_env import PackedStates
+    from stratego_env_amd.vec_env import VecStrategoEnv
+    name, n = 'tiny', 5
+    ru = orc.OracleRules(4, 4)
+    m1 = np.zeros((n, 4, 4), dtype=np.int8); m2 = np.zeros((n, 4, 4), dtype=np.int8)
+    m1[:, 0, 0] = 5; m1[:, 0, 3] = 11; m2[:, 0, 0] = 5; m2[:, 0, 3] = 11
+    env = VecStrategoEnv(name, n, seed=1, auto_reset=False, human_inits=False, placement='plain')
+    env.reset(torch.from_numpy(m1), torch.from_numpy(m2))
+    states, players = (_np(t) for t in env.export_state())
+    moves = [((0, 0), (1, 0)), ((3, 3), (2, 3)), ((1, 0), (0, 0)), ((2, 3), (3, 3)), ((0, 0), (1, 0)), ((3, 3), (2, 3)), ((1, 0), (0, 0)), ((2, 3), (3, 3))]
+    one = np.asarray([ru.get_action_1d_index_from_positions(*s, *e) for s, e in moves], dtype=np.int32)
+    acts = np.tile(one, (n, 1))
+    lengths = np.asarray([8, 7, 6, 8, 0], dtype=np.int32)
+    acts_t, lengths_t = torch.from_numpy(acts).cuda(), torch.from_numpy(lengths).cuda()
+    pool = PackedStates(name, n)
+    seen = {}
+    for allow in (False, True):
+        for skip in (False, True):
+            flags = dict(skip_invalid=skip, actions_1d=True, allow_piece_oscillation=allow)
+            res = pool.replay(env, acts_t, lengths=lengths_t, **flags)
+            want = _compare(name, pool, res, states, players, acts, lengths, None, flags, (name, allow, skip))
+            seen[allow, skip] = (want[5].tolist(), want[6].tolist(), want[7].tolist())
+    assert seen[False, False] == ([6, 6, 6, 6, 0], [6, 6, 6, 6, 0], [2, 2, 0, 2, 0])        # the seventh entry is the fourth oscillation
+    assert seen[False, True] == ([6, 6, 6, 6, 0], [8, 7, 6, 8, 0], [0, 0, 0, 0, 0])
+    assert seen[True, False] == seen[True, True] == ([8, 7, 6, 8, 0], [8, 7, 6, 8, 0], [0, 0, 0, 0, 0])
+    pool.close(); env.close()
+
+
+# ---- K: the example ------------------------------------------------------------------------------------------------------------------------
+def test_the_trajectory_example_runs():
+    from stratego_env_amd.examples.replay_trajectory import rerender_check
+    checked = rerender_check('fives', games=8, steps=12, samples=6)
+    assert checked == 6

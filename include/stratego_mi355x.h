@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define SGX_ABI_VERSION 15
+#define SGX_ABI_VERSION 15       /* (sgx_count_moves, sgx_expand_all and sgx_children_io are additions within v15: new entry points and a new
+                                    struct, no existing layout or signature changed) */
 #define SGX_MAX_CELLS 1024       /* rows*cols <= 1024 (largest reference variant: 15x15 = 225; the reference's StrategoProceduralEnv
                                     takes any size, penv:27-36: boards of more than 256 cells use 10-bit cell indices in the record) */
 #define SGX_PO_OBS_CHANNELS 67   /* impl:1332 */
@@ -133,6 +134,8 @@ typedef struct sgx_step_io {
  *   sgx_determinize              src_index_dev, hidden_dev 4
  *   sgx_playout                  src_index_dev, reward_dev, length_dev 4; done_dev, ending_invalid_dev, player_dev 1
  *   sgx_replay                   src_index_dev, actions_dev, lengths_dev, applied_dev, consumed_dev, reward_dev 4; stop_dev, done_dev, ending_invalid_dev, player_dev 1
+ *   sgx_count_moves              src_index_dev, counts_dev 4; offsets_dev 16
+ *   sgx_expand_all               src_index_dev, parent_dev, action_dev, reward_dev 4; offsets_dev 16; done_dev, ending_invalid_dev, player_dev 1
  *   sgx_mem_probe        ptr_dev 1024;   sgx_store_probe   ptr_dev 16
  * Change note: these rejections are new error returns for pointers that were never legal (the stores they guard were issued unchecked
  * before; only sgx_decode_obs and the compact path refused them); no struct or signature changed, so SGX_ABI_VERSION stays. */
@@ -275,6 +278,7 @@ int sgx_set_steps_barrier(sgx_env *h, int32_t mode);
 #define SGX_LAUNCH_MULTI_STEP_WAVE 3   /* one wave per game, all steps of the call in one launch: the boards stay in LDS between the steps */
 #define SGX_LAUNCH_PLAYOUT 4     /* sgx_playout: one wave per game, every move of the playout in one launch (set on dst) */
 #define SGX_LAUNCH_REPLAY 5      /* sgx_replay: one wave per game, every entry of the action list in one launch (set on dst) */
+#define SGX_LAUNCH_CHILDREN 6    /* sgx_expand_all: one wave per child, root found from the offsets, mask regenerated, move applied (set on dst) */
 int sgx_last_launch_kind(const sgx_env *h);
 
 /* Shares of the eight XCDs in a launch of sgx_step / sgx_observe.  Under a saturating write stream the odd XCDs of MI355X drain their
@@ -661,6 +665,49 @@ typedef struct sgx_replay_io {
     int32_t max_len, flags;
 } sgx_replay_io;                  /* 9 pointers + 3 int64 + 2 int32 = 104 bytes */
 int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_replay_io *io, void *stream);
+
+/* Expand all: every valid move of every root, pool to pool -- "all children of these nodes", what MCTS / ISMCTS node expansion, an
+ * exhaustive shallow search and a perft-style check of the move generator start with -- without a mask, a nonzero() or an action list on
+ * the host.  sgx_count_moves counts the moves per root and scans the counts into offsets; sgx_expand_all writes a window of the children.
+ * THE RULE (tests/children_rule.py restates it on the CPU oracle, bit for bit):
+ *   For root slot i in [0, n_roots): pos = record src_index[i] of src (i when the index is NULL); m = the valid-action mask of pos's mover
+ *   in its own perspective (the bits sgx_observe writes for that record).
+ *   count[i] = the number of moves in m: 0 for a finished game and for a mover without a move -- the no-op entry is never a child.
+ *   offsets[0] = 0, offsets[i + 1] = offsets[i] + count[i], as int64; total = offsets[n_roots].
+ *   Child c in [0, total): its root is the i with offsets[i] <= c < offsets[i + 1], its rank k = c - offsets[i], its action a the k-th set
+ *   entry of m in ascending flat order (the order the playout's sampler and sgx_sample_valid count in).
+ *   A call covers the window [first_child, first_child + n_children): slot j of dst belongs to child c = first_child + j.
+ *   c < total: dst[j] = pos advanced by a exactly as sgx_step applies an action (the same endings, no auto-reset); parent[j] = i (the
+ *   position in the root list, not src_index[i]); action[j] = a, the flat spatial index in the mover's perspective that sgx_step, sgx_replay
+ *   and sgx_choose_actions take -- with SGX_CHILDREN_ACTIONS_1D the absolute 1-D index sgx_expand takes (SGX_STEP_ACTIONS_1D), through the
+ *   map of the 1-D mask emission (SGX_STEP_MASK_1D); the ORDER of the children is the perspective order in both forms; reward[j], done[j],
+ *   ending_invalid[j], player[j] = what that step reports for the child.
+ *   c >= total: record j of dst is left as it was, parent[j] = action[j] = -1, the other outputs are not written.
+ *   The kernel regenerates the root's mask and so knows the true count: a rank k >= count[i] (offsets that do not belong to these roots) is
+ *   a "no child" slot like c >= total, never an out-of-range read; the search of offsets takes a constant number of steps and stays inside
+ *   [0, n_roots) whatever the array holds (offsets_dev must hold n_roots + 1 readable entries).
+ * Nothing is drawn: dst's seed does not enter.  src is only read.
+ * SGX_EINVAL, before anything is launched: a NULL handle or io; handles of different devices or variants; src == dst (children would
+ * overwrite roots); a dst with a start pool set; n_children > dst's envs; a negative n_roots, n_children or first_child (n_roots < 2^31);
+ * without an index n_roots > src's envs; unknown flag bits; offsets_dev NULL; a misaligned pointer (offsets_dev 16 bytes; src_index_dev,
+ * counts_dev, parent_dev, action_dev, reward_dev 4; the byte tensors any address).  n_roots == 0: sgx_count_moves writes offsets[0] = 0 and
+ * launches no kernel; n_children == 0: sgx_expand_all launches nothing.  sgx_expand_all sets dst's sgx_last_launch_kind to
+ * SGX_LAUNCH_CHILDREN.  The scan's scratch (and the counts when counts_dev is NULL) lives in the src handle: allocated at first use, freed
+ * by sgx_destroy; no workgroup of the scan waits on another.  Added without a change to an existing struct or signature: SGX_ABI_VERSION
+ * stays.  Reference counterpart: none -- get_next_state over np.nonzero(get_valid_moves_as_1d_mask) in a Python loop (penv:96-155). */
+#define SGX_CHILDREN_ACTIONS_1D 1    /* action_dev holds absolute 1-D indices (as sgx_expand takes); default: flat spatial, mover's perspective */
+int sgx_count_moves(sgx_env *src, const int32_t *src_index_dev, int64_t n_roots, int32_t *counts_dev /* [n_roots], nullable */,
+                    int64_t *offsets_dev /* [n_roots + 1] */, void *stream);
+typedef struct sgx_children_io {
+    const int64_t *offsets_dev;   /* [n_roots + 1], from sgx_count_moves */
+    int32_t *parent_dev, *action_dev;            /* [n_children] out, nullable */
+    float   *reward_dev;          /* [n_children][2] out, nullable: rewards[+1], rewards[-1] of the step that made the child */
+    uint8_t *done_dev, *ending_invalid_dev;      /* [n_children] out, nullable */
+    int8_t  *player_dev;          /* [n_children] out, nullable: the mover at the child */
+    int64_t n_roots, first_child, n_children;
+    int32_t flags, reserved;
+} sgx_children_io;                /* 7 pointers + 3 int64 + 2 int32 = 88 bytes */
+int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_children_io *io, void *stream);
 
 /* Per-env bookkeeping: int32 [N][4] = {turn count, game number, game_over, current player}. */
 int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream);

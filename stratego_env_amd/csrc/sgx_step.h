@@ -289,9 +289,13 @@ __device__ __forceinline__ auto first_of(const StepCarry *carry) {
 // has a move (gen_any), and pp is unused.  An invalid action leaves the carry's turn counter where it was: every valid action on an
 // unfinished game advances it (the no-op of a mover without a move included) and a finished game is never stepped, so the caller reads
 // validity from the counter and StepCarry keeps its size.
+// 5 / 6 (count_kernel / children_kernel, sgx_children.h): passes over a ROOT like 1 and 3 -- the record staged, no move, nothing stored, nothing
+// drawn, pp unused -- that generate the mover's mask with its bits and answer through carry->na: 5 leaves the NUMBER of valid moves there
+// (what gen_mask returns: 0 for a finished game and for a mover without a move); 6 takes a rank k from carry->na and leaves the k-th valid
+// action in ascending flat order (kth_valid), or -1 where the root has no more than k moves.  The child itself is PLAY 4 on that action.
 template <int PLAY, class KP>
 __device__ __forceinline__ int mode_of(const KP &P) {
-    if constexpr (PLAY != 0) return (PLAY == 1 || PLAY == 3) ? 1 : 0;
+    if constexpr (PLAY != 0) return (PLAY == 1 || PLAY == 3 || PLAY >= 5) ? 1 : 0;
     else return P.mode;
 }
 template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, bool POOL = false, class KP = KParams, class PPT = PoolParams, int PLAY = 0>
@@ -538,7 +542,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     int qi = player == 1 ? 0 : 1;
     // Launches of the no-observation kind that want neither the mask nor a next action (search expansion, sgx_expand; logic-only steps)
     // only need to know WHETHER the next mover has a move (the opponent-stuck ending): no mask bits, no counts, one cell per ray.
-    const bool want_bits = PLAY < 3 && (PLAY != 0 || !NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr));
+    const bool want_bits = PLAY >= 5 || (PLAY < 3 && (PLAY != 0 || !NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr)));
 #ifdef SGX_ABLATE
     if (SGX_ABLATED(P.map_arg, 3)) return;                              // staging only
     int nvalid = gen_mask(L, qi, over, lane, P.map_arg);
@@ -699,7 +703,15 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
         if (io_fobs) render(FS{}, true, qi, io_fobs + env * (int64_t)(RC * FS::NCH));
     }
     STAMP(6);   // obs stores issued
-    if constexpr (PLAY == 1 || PLAY == 2) {
+    if constexpr (PLAY == 5) {
+        carry->na = nvalid;
+    } else if constexpr (PLAY == 6) {
+        // (kth_valid is run by all lanes of the wave's games alike: the rank is clamped into the mask -- the no-op entry where there is no
+        // move -- and the answer dropped where it was not a rank of this root)
+        const int k = carry->na;
+        const int na = kth_valid(L, max(min(k, nvalid - 1), 0), lane);
+        carry->na = (k >= 0 && k < nvalid) ? na : -1;
+    } else if constexpr (PLAY == 1 || PLAY == 2) {
         const int total = nvalid == 0 ? 1 : nvalid;
         const uint32_t k = rng_below(sgx_rng(P.seed, (uint64_t)(P.env_id_offset + env), pp->draw, STREAM_PLAYOUT, (uint32_t)turn), (uint32_t)total);
         carry->na = kth_valid(L, (int)k, lane);

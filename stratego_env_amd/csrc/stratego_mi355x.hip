@@ -83,6 +83,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 #include "sgx_step.h"
 #include "sgx_playout.h"
 #include "sgx_replay.h"
+#include "sgx_children.h"
 #include "sgx_lane.h"
 #include "sgx_lane_kernel.h"
 #include "sgx_aux_kernels.h"
@@ -144,6 +145,10 @@ struct sgx_env {
     int64_t n_pool;
     int pool_flags;
     int32_t *start_index;
+    // sgx_count_moves: the counts when the caller takes none, and the block sums of the offsets scan (created on first use, grown on demand)
+    int32_t *count_scratch;
+    int64_t *scan_sums;
+    int64_t count_scratch_cap, scan_sums_cap;
 };
 
 namespace {
@@ -515,6 +520,8 @@ SGX_API int sgx_destroy(sgx_env *h) {
     if (h->ring_tab_dev) (void)hipFree(h->ring_tab_dev);
     if (h->ring_tab_host) (void)hipHostFree(h->ring_tab_host);
     if (h->ring_tab_ev) (void)hipEventDestroy(h->ring_tab_ev);
+    if (h->count_scratch) (void)hipFree(h->count_scratch);
+    if (h->scan_sums) (void)hipFree(h->scan_sums);
     delete h;
     return SGX_OK;
 }
@@ -2164,6 +2171,111 @@ SGX_API int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
         })) return rc;
     HIP_TRY(hipGetLastError());
     dst->last_kind = SGX_LAUNCH_REPLAY;
+    return SGX_OK;
+}
+
+namespace {
+// handle scratch of at least `elems` elements (hipFree waits for the launches that still read the old one)
+template <class T>
+int grow_scratch(T **buf, int64_t *cap, int64_t elems) {
+    if (*cap >= elems) return SGX_OK;
+    if (*buf) { HIP_TRY(hipFree(*buf)); *buf = nullptr; *cap = 0; }
+    const int64_t want = elems + elems / 2;
+    HIP_TRY(hipMalloc((void **)buf, (size_t)want * sizeof(T)));
+    *cap = want;
+    return SGX_OK;
+}
+}  // namespace
+
+SGX_API int sgx_count_moves(sgx_env *src, const int32_t *src_index_dev, int64_t n_roots, int32_t *counts_dev, int64_t *offsets_dev, void *stream) {
+    if (!src) return fail(SGX_EINVAL, "sgx_count_moves: handle is NULL%s");
+    if (!offsets_dev) return fail(SGX_EINVAL, "sgx_count_moves: offsets_dev is NULL%s");
+    if (n_roots < 0 || n_roots > 0x7fffffff) return fail(SGX_EINVAL, "sgx_count_moves: n_roots must be in [0, 2^31)%s");
+    if (!src_index_dev && n_roots > src->n_envs) return fail(SGX_EINVAL, "sgx_count_moves: without src_index_dev n_roots must not exceed the handle's envs%s");
+    if (int rc = check_aligned("sgx_count_moves", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_count_moves", "counts_dev", counts_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_count_moves", "offsets_dev", offsets_dev, 16)) return rc;
+    SGX_ON_DEVICE(src->device);
+    if (n_roots == 0) {
+        HIP_TRY(hipMemsetAsync(offsets_dev, 0, sizeof(int64_t), (hipStream_t)stream));
+        return SGX_OK;
+    }
+    const int64_t n_blocks = (n_roots + SCAN_BLOCK - 1) / SCAN_BLOCK;
+    if (!counts_dev) {
+        if (int rc = grow_scratch(&src->count_scratch, &src->count_scratch_cap, n_roots)) return rc;
+        counts_dev = src->count_scratch;
+    }
+    if (int rc = grow_scratch(&src->scan_sums, &src->scan_sums_cap, n_blocks)) return rc;
+    CountParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.k = make_params(src);           // (io all NULL / 0; nothing of the handle is written)
+    sp.k.mode = 1;
+    sp.k.n_envs = n_roots;
+    sp.k.src_boards = src->boards;
+    sp.k.src_index = src_index_dev;
+    sp.counts = counts_dev;
+    int32_t w[8];
+    launch_setup(src, sp.k, 1, w);
+    if (int rc = for_geometry(src, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            with_half_wave<R, C, 8>(src, [&](auto var) {           // the geometry of the logic-only launches
+                constexpr int VAR = decltype(var)::value;
+                using G = Geo<R, C, VAR>;
+                const unsigned grid = geo_grid<G>(sp.k, w);
+                count_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
+            });
+        })) return rc;
+    HIP_TRY(hipGetLastError());
+    scan_sums_kernel<<<(unsigned)n_blocks, SCAN_BLOCK, 0, (hipStream_t)stream>>>(counts_dev, src->scan_sums, n_roots);
+    scan_bases_kernel<<<1, SCAN_BLOCK, 0, (hipStream_t)stream>>>(src->scan_sums, n_blocks);
+    scan_offsets_kernel<<<(unsigned)n_blocks, SCAN_BLOCK, 0, (hipStream_t)stream>>>(counts_dev, src->scan_sums, offsets_dev, n_roots);
+    HIP_TRY(hipGetLastError());
+    return SGX_OK;
+}
+
+SGX_API int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_children_io *io, void *stream) {
+    if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_expand_all: handle or io is NULL%s");
+    if (int rc = same_variant(dst, src)) return rc;
+    if (src == dst) return fail(SGX_EINVAL, "sgx_expand_all: src == dst (children would overwrite roots); expand into a second handle%s");
+    if (dst->pool) return fail(SGX_EINVAL, "sgx_expand_all: dst has a start pool set (an expansion never restarts a game); clear it or expand into another handle%s");
+    if (io->n_roots < 0 || io->n_roots > 0x7fffffff || io->n_children < 0 || io->first_child < 0)
+        return fail(SGX_EINVAL, "sgx_expand_all: n_roots (below 2^31), n_children and first_child must not be negative%s");
+    if (io->n_children > dst->n_envs) return fail(SGX_EINVAL, "sgx_expand_all: n_children exceeds dst's envs%s");
+    if (!src_index_dev && io->n_roots > src->n_envs) return fail(SGX_EINVAL, "sgx_expand_all: without src_index_dev n_roots must not exceed src's envs%s");
+    if (io->flags & ~SGX_CHILDREN_ACTIONS_1D) return fail(SGX_EINVAL, "sgx_expand_all: unknown flag bits%s");
+    if (!io->offsets_dev) return fail(SGX_EINVAL, "sgx_expand_all: offsets_dev is NULL%s");
+    if (int rc = check_aligned("sgx_expand_all", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_expand_all", "offsets_dev", io->offsets_dev, 16)) return rc;
+    if (int rc = check_aligned("sgx_expand_all", "parent_dev", io->parent_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_expand_all", "action_dev", io->action_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_expand_all", "reward_dev", io->reward_dev, 4)) return rc;
+    dst->last_kind = SGX_LAUNCH_CHILDREN;
+    if (io->n_children == 0) return SGX_OK;
+    SGX_ON_DEVICE(dst->device);
+    ChildrenParams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.k = make_params(dst);           // (io all NULL / 0: spatial actions in the mover's perspective, no auto-reset, no per-step output)
+    sp.k.mode = 0;
+    sp.k.n_envs = io->n_children;
+    sp.k.src_boards = src->boards;
+    sp.k.src_index = src_index_dev;
+    sp.ch.offsets = io->offsets_dev;
+    sp.ch.parent = io->parent_dev; sp.ch.action = io->action_dev;
+    sp.ch.reward = io->reward_dev; sp.ch.done = io->done_dev; sp.ch.ending_invalid = io->ending_invalid_dev; sp.ch.player = io->player_dev;
+    sp.ch.n_roots = io->n_roots; sp.ch.first_child = io->first_child;
+    sp.ch.actions_1d = (io->flags & SGX_CHILDREN_ACTIONS_1D) ? 1 : 0;
+    int32_t w[8];
+    launch_setup(dst, sp.k, 1, w);
+    if (int rc = for_geometry(dst, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            with_half_wave<R, C, 8>(dst, [&](auto var) {           // the geometry of the logic-only launches
+                constexpr int VAR = decltype(var)::value;
+                using G = Geo<R, C, VAR>;
+                const unsigned grid = geo_grid<G>(sp.k, w);
+                children_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
+            });
+        })) return rc;
+    HIP_TRY(hipGetLastError());
     return SGX_OK;
 }
 

@@ -450,6 +450,37 @@ class BatchedStrategoProceduralEnv:
         finally:
             src.close()
 
+    def expand_all(self, states, players):
+        """Every valid move of every state applied: all children of a batch of nodes (PackedStates.expand_all: pack -> count -> expand into a
+        scratch pool of at most batch_size records, window after window -> unpack, for callers on the reference layout).
+        -> (children int64 [M,34,R,C], child_players int8 [M], parent int32 [M], action_1d int32 [M]): child j is
+        get_next_state(states[parent[j]], players[parent[j]], action_1d[j]); parents ascend, and the children of one parent come in the
+        ascending order of the mover's perspective mask (PackedStates.expand_all), which for player -1 is the descending order of start
+        cells in absolute coordinates.  Finished states and movers without a move have no child.  M is read from the device (one
+        synchronisation)."""
+        src = self.pack(states, players)
+        try:
+            _, offsets = src.count_moves()
+            total = int(offsets[-1])
+            cap = max(1, min(total, self.batch_size))
+            dst = self.new_packed(cap)
+            try:
+                out = ([], [], [], [])
+                for first in range(0, total, cap):
+                    m = min(cap, total - first)
+                    res = dst.expand_all(src, offsets=offsets, first_child=first, n=m, actions_1d=True)
+                    st, pl = dst.unpack()
+                    for lst, t in zip(out, (st, pl, res.parent, res.action)):
+                        lst.append(t[:m])
+                if not out[0]:
+                    st, pl = dst.unpack()
+                    return st[:0], pl[:0], torch.empty((0,), dtype=torch.int32, device=self.device), torch.empty((0,), dtype=torch.int32, device=self.device)
+                return tuple(torch.cat(lst) for lst in out)
+            finally:
+                dst.close()
+        finally:
+            src.close()
+
     def close(self):
         self._vec.close()
 
@@ -481,6 +512,21 @@ class ReplayResult:
     def __init__(self, applied, consumed, stop, reward, done, ending_invalid, player):
         self.applied, self.consumed, self.stop = applied, consumed, stop
         self.reward, self.done, self.ending_invalid, self.player = reward, done, ending_invalid, player
+
+    value_for = PlayoutResult.value_for
+
+
+class ChildrenResult:
+    """What PackedStates.expand_all reports per slot of its window (device tensors): parent int32 (the position of the child's root in the root
+    list, -1 = no child in this slot), action int32 (the move that made the child, -1 = no child), and of the step that made the child
+    reward float32 [n,2], done uint8, ending_invalid uint8, player int8 (the mover AT the child) -- these four are unwritten where parent is
+    -1.  offsets int64 [n_roots + 1] are the roots' child numbers (count_moves) and total = offsets[n_roots] a device scalar: int(total) is
+    the one synchronisation a caller may choose."""
+
+    def __init__(self, parent, action, reward, done, ending_invalid, player, offsets, total):
+        self.parent, self.action = parent, action
+        self.reward, self.done, self.ending_invalid, self.player = reward, done, ending_invalid, player
+        self.offsets, self.total = offsets, total
 
     value_for = PlayoutResult.value_for
 
@@ -597,6 +643,46 @@ class PackedStates:
         call with a live env as the destination.)"""
         return self._vec.replay(src, actions, lengths=lengths, src_index=src_index, skip_invalid=skip_invalid, actions_1d=actions_1d,
                                 allow_piece_oscillation=allow_piece_oscillation)
+
+    def count_moves(self, index=None):
+        """-> (counts int32 [n], offsets int64 [n + 1]): the valid moves of record index[i] (None: every record in order) and their exclusive
+        scan, on the device without a synchronisation (VecStrategoEnv.count_moves)."""
+        return self._vec.count_moves(index)
+
+    def expand_all(self, src, src_index=None, offsets=None, first_child=0, n=None, actions_1d=False):
+        """All children of the roots src[src_index[i]] (None: every record of src in order), no action list needed: slot j of this pool
+        becomes child first_child + j of the list of all children -- roots in order, each root's moves in the ascending flat order of its
+        mover's perspective mask -- in one launch (sgx_expand_all; the rule is in include/stratego_mi355x.h).  `src`: another PackedStates or
+        a live VecStrategoEnv of the same variant, only read.  offsets: what count_moves(src_index) of `src` returned (None: counted here);
+        n: the slots of this call's window (None: the whole pool) -- a level with more children than the pool is walked with first_child =
+        0, n, 2n, ...; slots past the last child keep their records and report parent = action = -1.  actions_1d: `action` holds absolute
+        1-D indices as `expand` takes them instead of flat spatial indices in the mover's perspective as env.step() takes them (the order of
+        the children is the same).  -> ChildrenResult (no synchronisation; int(res.total) is the caller's)."""
+        vec = self._vec
+        src_vec = src._vec if isinstance(src, PackedStates) else src
+        if src_vec is vec:
+            raise ValueError("expand_all inside one pool would overwrite roots with children: expand into another pool")
+        dev = self.device
+        si = None if src_index is None else torch.as_tensor(src_index).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        n_roots = src_vec.num_envs if si is None else int(si.numel())
+        if offsets is None:
+            offsets = src_vec.count_moves(si)[1]
+        elif not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.device != dev or not offsets.is_contiguous() \
+                or offsets.numel() != n_roots + 1:
+            raise ValueError("offsets must be the contiguous int64 device tensor [%d] that count_moves returned for these roots" % (n_roots + 1))
+        n = self.n if n is None else int(n)
+        m = max(n, 0)
+        res = ChildrenResult(torch.empty((m,), dtype=torch.int32, device=dev), torch.empty((m,), dtype=torch.int32, device=dev),
+                             torch.empty((m, 2), dtype=torch.float32, device=dev), torch.empty((m,), dtype=torch.uint8, device=dev),
+                             torch.empty((m,), dtype=torch.uint8, device=dev), torch.empty((m,), dtype=torch.int8, device=dev),
+                             offsets, offsets[n_roots])
+        p = (lambda t: t.data_ptr()) if m else (lambda t: None)
+        io = _lib.SgxChildrenIO(offsets.data_ptr(), p(res.parent), p(res.action), p(res.reward), p(res.done), p(res.ending_invalid), p(res.player),
+                                n_roots, int(first_child), n, _lib.CHILDREN_ACTIONS_1D if actions_1d else 0, 0)
+        with torch.cuda.device(dev):
+            _lib.check(vec._L.sgx_expand_all(vec._h, src_vec._h, None if si is None or n_roots == 0 else si.data_ptr(), io, vec._stream()), vec._L)
+        vec._next_actions_fresh = False
+        return res
 
     @property
     def last_launch_kind(self):

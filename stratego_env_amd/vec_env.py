@@ -831,6 +831,20 @@ class VecStrategoEnv:
         self._next_actions_fresh = False
         return res
 
+    def count_moves(self, index=None):
+        """The number of valid moves of every game's mover and their exclusive scan (sgx_count_moves; the rule is in
+        include/stratego_mi355x.h): root slot i is game index[i] (int32 [n], any length, repeats allowed; None: every game in order).
+        -> (counts int32 [n], offsets int64 [n + 1]) on the device, no synchronisation: counts[i] is 0 for a finished game and for a mover
+        without a move, offsets[i] is the number of the first child of root i and offsets[n] the total (PackedStates.expand_all takes them)."""
+        dev = self.device
+        idx = None if index is None else torch.as_tensor(index).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        n = self.num_envs if idx is None else int(idx.numel())
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._L.sgx_count_moves(self._h, _ptr(idx) if n else None, n, _ptr(counts) if n else None, _ptr(offsets), self._stream()), self._L)
+        return counts, offsets
+
     def sample_valid_actions(self, mask=None, out=None):
         """Uniformly random valid action per env from `mask` (default: the current one) -- maenv:830-834."""
         own = mask is None or mask is self.mask

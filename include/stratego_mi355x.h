@@ -214,7 +214,11 @@ int sgx_build_original_obs_lut(const sgx_config *cfg, int32_t full, float *lut);
 
 /* StrategoMultiAgentEnv.__init__ (maenv:318-445) for a batch: allocates the device state of n_envs games on
  * `device`.  Env i of this handle has global id env_id_offset + i; all random draws are keyed by
- * (seed, global id, game number, turn), so trajectories do not depend on how the batch is sharded. */
+ * (seed, global id, game number, turn), so trajectories do not depend on how the batch is sharded.
+ * A limit of the key: the RNG's first mix takes seed + 0x9E3779B97F4A7C15 * (global id + 1), so (seed, g) and
+ * (seed + 0x9E3779B97F4A7C15, g - 1) name the same stream: two handles whose seeds differ by exactly that constant (mod 2^64) play the
+ * same games shifted by one env id.  Seeds that differ by anything else -- s + 1, s + (1 << 32) -- give independent games
+ * (tests/test_draws_cpu.py, tests/test_gpu_draws.py).  The arithmetic stays as it is: recorded trajectories are keyed on it. */
 int sgx_create(const sgx_config *cfg, int64_t n_envs, int device, uint64_t seed, int64_t env_id_offset, sgx_env **out);
 int sgx_destroy(sgx_env *h);
 

@@ -217,6 +217,10 @@ struct KParams {
     // sums the events of a key (the first one speaks for all); 0 for every variant of the reference, whose lists never hold duplicates.
     int32_t multi_ev;
     int32_t compact_stride;   // SGX_STEP_COMPACT_OBS: bytes of one game's compact observation record (sgx_compact_obs_stride)
+    // nt_stores only: the leading 128-byte lines of each game's partial observation that leave as plain stores all the same in the
+    // multi-step kernels of kind 0 (sgx_store_policy.h); 0 = none.  (A halfword in what was padding: the argument block of every kernel
+    // keeps its size and offsets.)
+    int16_t plain_lines;
     // functional-API instantiation only (sgx_expand): game i is read from record src_index[i] (i when NULL) of ANOTHER handle's
     // records and written to record i of this one, whether or not the move was valid
     const int8_t *src_boards;

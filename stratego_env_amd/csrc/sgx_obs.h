@@ -187,8 +187,8 @@ __device__ inline int load_compact(Lds<G, NB> &L, const uint8_t *__restrict__ sr
 // NT: lines this wave writes whole leave as non-temporal stores -- chosen per launch, see KParams::nt_stores.
 // STRIDE: lanes that share the sweep -- the game's LPG lanes, or every thread of the workgroup (`lane` = thread index) when a whole
 // workgroup emits one game (single_kernel).
-template <class G, class Spec, bool CHECKED, bool NT, int STRIDE = G::LPG, int NB>
-__device__ inline void emit_codes(const Lds<G, NB> &L, float *__restrict__ dst, int lane) {
+template <class G, class Spec, bool CHECKED, bool NT, int STRIDE = G::LPG, bool SPLIT = false, int NB>
+__device__ inline void emit_codes(const Lds<G, NB> &L, float *__restrict__ dst, int lane, int plain_lines = 0) {
     constexpr int RC = G::RC, NCH = Spec::NCH;
     const uint16_t *n16 = reinterpret_cast<const uint16_t *>(L.nib);
     if constexpr (RC % 4 == 0) {
@@ -218,7 +218,11 @@ __device__ inline void emit_codes(const Lds<G, NB> &L, float *__restrict__ dst, 
                 esc = ((y - 0x1111u) & ~y & 0x8888u) != 0;                            // some nibble of y is 0
             }
             if constexpr (NT) {
+                // SPLIT (the multi-step kernels of kind 0): plain_lines (launch-uniform, KParams::plain_lines) leading lines of the observation go the plain
+                // way too, whole lines only -- a multi-step launch writes them again while they are still in the Infinity Cache.  4-aligned
+                // boards only: the odd boards' branch below keeps every whole line non-temporal.
                 bool edge = ((q + l0) >> 3) == first_line || ((q + l0) >> 3) == last_line;
+                if constexpr (SPLIT) edge = edge || ((q + l0) >> 3) < plain_lines;
                 if constexpr (CHECKED) {
                     // a line with a left-out quad is completed by patch_uncoded's 16-byte store: both parts go through L2, which merges them
                     // into one whole-line write-back; non-temporal, the line reached memory as two partial writes (Standard 300 steps into

@@ -597,11 +597,17 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
             const int n_unc = build_codes<G, Spec>(L, tmpl, codetab, full ? glut_f : glut_p, q,
                                                    n_events, rp0, rp1, lane, P.piece_counts, raw, P.multi_ev != 0);
             if constexpr (RC % 4 == 0) {
+                // the multi-step kernels of kind 0 (steps_kernel, steps_kernel_pool; partial observation only) give the leading lines of the
+                // observation to plain stores (KParams::plain_lines); every other kernel that plays this step keeps the text it had -- BOTH
+                // mode too, whose instantiations took a VGPR or four bytes of scratch more with a count per observation
+                constexpr bool SPLIT_LINES = PERSIST_ != 0 && PLAY == 0 && KIND == 0;
+                int plain_lines = 0;
+                if constexpr (SPLIT_LINES) plain_lines = P.plain_lines;
                 if (n_unc == 0) {
-                    if (P.nt_stores) emit_codes<G, Spec, false, true>(L, dst, lane);
+                    if (P.nt_stores) emit_codes<G, Spec, false, true, G::LPG, SPLIT_LINES>(L, dst, lane, plain_lines);
                     else emit_codes<G, Spec, false, false>(L, dst, lane);
                 } else {
-                    if (P.nt_stores) emit_codes<G, Spec, true, true>(L, dst, lane);
+                    if (P.nt_stores) emit_codes<G, Spec, true, true, G::LPG, SPLIT_LINES>(L, dst, lane, plain_lines);
                     else emit_codes<G, Spec, true, false>(L, dst, lane);
                     patch_uncoded<G, Spec>(L, dst, n_unc, lane);
                 }

@@ -76,6 +76,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 
 }  // namespace
 
+#include "sgx_store_policy.h"
 #include "sgx_layout.h"
 #include "sgx_obs.h"
 #include "sgx_mask.h"
@@ -114,6 +115,11 @@ struct sgx_env {
     int xcd_explicit;            // xcd_w was set by sgx_set_xcd_shares: it overrides the skew rule
     int32_t xcd_w[8];            // shares of the eight XCDs, per mille of the mean share (sum 8000)
     int nt_mode;                 // sgx_set_nt_stores: -1 = by the launch's output size, 0 = never, 1 = always
+    int plain_lines_forced;      // SGX_NT_PLAIN_LINES: -1 = the rule of sgx_store_policy.h, else non-temporal stores with this many leading plain lines
+    int cus;                     // compute units of the device
+    int steps_wg_per_cu[2][2];   // resident workgroups per CU of steps_kernel / steps_kernel_pool<R, C, KIND 0 | 1> (occupancy query at first use; 0 = not asked yet)
+    int policy_debug;            // SGX_STORE_POLICY_DEBUG=1: steps_policy prints what it chose to stderr whenever the choice changes
+    int policy_printed[4];       // ... the last choice printed (sets, nt_stores, plain_lines, resident workgroups per CU)
     int lane_mode;               // sgx_set_lane_kernel: 0 = never the lane-per-game kernel, otherwise wherever it is eligible
     float placement_target_us;   // sgx_set_placement_target: sgx_alloc_outputs searches on until a candidate is within 3 % of it (0 = its own stop rules)
     hipStream_t chain_stream[SGX_MAX_CHAINS];   // sgx_rollout: created on first use
@@ -427,6 +433,16 @@ SGX_API int sgx_create(const sgx_config *cfg, int64_t n_envs, int device, uint64
         if (!strcmp(e, "0")) h->nt_mode = 0;
         else if (!strcmp(e, "1")) h->nt_mode = 1;
     }
+    h->plain_lines_forced = -1;
+    if (const char *e = getenv("SGX_NT_PLAIN_LINES")) {     // SGX_NT_PLAIN_LINES=<count>: non-temporal stores with that many leading plain lines; -1 = auto
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);                  // ("auto", "" or any other text that is not a number: unset)
+        if (end != e && *end == 0) h->plain_lines_forced = v < 0 ? -1 : v > 0x7FFF ? 0x7FFF : (int)v;   // (KParams carries it in a halfword; no board has 2,600 lines)
+    }
+    if (const char *e = getenv("SGX_STORE_POLICY_DEBUG")) {
+        h->policy_debug = !strcmp(e, "1");
+        h->policy_printed[0] = -1;
+    }
     h->lane_mode = -1;
     h->general_states = 1;
     if (const char *e = getenv("SGX_GENERAL_STATES")) h->general_states = atoi(e);
@@ -700,11 +716,16 @@ SGX_API int sgx_reset(sgx_env *h, const uint8_t *env_select_dev, const int8_t *p
 }
 
 // Beyond what the 256 MiB Infinity Cache absorbs a launch's kernels use non-temporal stores for the lines a wave writes whole (measured
-// crossover between 281 and 316 MB on four board sizes, sgx_obs.h).
-constexpr int64_t CACHE_FIT_BYTES = (int64_t)300 * 1000 * 1000;
-static bool past_cache(int64_t bytes) { return bytes > CACHE_FIT_BYTES; }
-// non-temporal stores for a launch that writes `bytes`: sgx_set_nt_stores, else by the size
-static int nt_for(const sgx_env *h, int64_t bytes) { return h->nt_mode < 0 ? (past_cache(bytes) ? 1 : 0) : h->nt_mode; }
+// crossover between 281 and 316 MB on four board sizes, sgx_obs.h).  What has to fit is what is written between two writes of one line:
+// the whole launch (x its output sets) for a per-step launch -- this rule; only what the RESIDENT games write for a multi-step launch of
+// steps_kernel, whose waves keep their games (steps_policy below).  Both rules and their constants (SGX_CACHE_FIT_BYTES,
+// SGX_PLAIN_BUDGET_BYTES): sgx_store_policy.h.
+static bool past_cache(int64_t bytes) { return !sgx_store_fits_launch(bytes); }
+// non-temporal stores for a launch that writes `bytes`: sgx_set_nt_stores, else SGX_NT_PLAIN_LINES, else by the size.  A forced count
+// comes with non-temporal stores for EVERY launch of the handle, whatever its size and kernel (lane kernels, states_kernel, small per-step
+// launches that the size rule would store plain): it is a knob for tests and sweeps of the split, not an override of the split alone, and
+// not a way to tune one ring in production.
+static int nt_for(const sgx_env *h, int64_t bytes) { return h->nt_mode >= 0 ? h->nt_mode : h->plain_lines_forced >= 0 ? 1 : (past_cache(bytes) ? 1 : 0); }
 
 // float32 observation bytes one launch writes
 static int64_t launch_obs_bytes(const sgx_env *h, const KParams &p) {
@@ -750,6 +771,9 @@ static void launch_setup(const sgx_env *h, KParams &p, int sets, int32_t *w) {
     p.map_mode = h->map_mode; p.map_arg = h->map_arg;
     const int64_t bytes = launch_obs_bytes(h, p) * sets;
     p.nt_stores = nt_for(h, bytes);
+    // sgx_set_nt_stores(1) keeps its meaning (every whole line non-temporal); the multi-step launches of steps_kernel get their own
+    // count from steps_policy
+    p.plain_lines = (int16_t)((h->nt_mode < 0 && h->plain_lines_forced >= 0) ? h->plain_lines_forced : 0);
     launch_shares(h, past_cache(bytes), w);                   // unequal XCD shares (sgx_layout.h: group_of_block)
 }
 // the grid of a launch that plays `games` games per workgroup (Geo::WPB x Geo::GPW, the lane kernels' 64) over the envs [env_first, n_envs)
@@ -992,6 +1016,46 @@ static int steps_launch(sgx_env *h, StepsParams &sp, KParams &p, const int32_t *
     });
 }
 
+// The store policy of a multi-step launch of steps_kernel<R, C, KIND> (4-aligned boards, float32 observations) where the launch's own size
+// asks for non-temporal stores and nothing is forced: by what the RESIDENT games rewrite (sgx_store_policy.h).  The resident workgroups per
+// CU come from the occupancy query, asked once per kernel and handle.
+template <int R, int C, int KIND>
+static int steps_policy(sgx_env *h, KParams &p, int32_t n_sets) {
+    if (h->nt_mode >= 0 || h->plain_lines_forced >= 0 || !p.nt_stores || (p.io.flags & SGX_STEP_ORIGINAL_CHANNELS)) return SGX_OK;
+    using G = Geo<R, C, 0>;
+    const int pool = h->pool ? 1 : 0;
+    if (!h->cus) {
+        int cus = 0;
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+        h->cus = cus;
+    }
+    if (!h->steps_wg_per_cu[KIND][pool]) {
+        int wgs = 0;
+        if (pool) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, steps_kernel_pool<R, C, KIND, 0>, 64 * G::WPB, 0));
+        else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, steps_kernel<R, C, KIND, 0>, 64 * G::WPB, 0));
+        h->steps_wg_per_cu[KIND][pool] = wgs > 0 ? wgs : 1;
+    }
+    const int64_t cells = (int64_t)R * C;
+    sgx_store_shape s;
+    s.cus = h->cus; s.wg_per_cu = h->steps_wg_per_cu[KIND][pool]; s.games_per_wg = G::WPB * G::GPW;
+    s.games = p.n_envs - p.env_first; s.sets = n_sets;
+    s.obs_bytes = p.io.obs_dev ? cells * lut_channels(false, false) * 4 : 0;
+    s.fobs_bytes = p.io.fobs_dev ? cells * lut_channels(true, false) * 4 : 0;
+    s.mask_bytes = p.io.mask_dev ? cells * h->K : 0;
+    // BOTH mode (kind 1): all plain where the rewrite set fits, no share otherwise -- its kernels do not read a count (sgx_step.h)
+    s.budget = SGX_PLAIN_BUDGET_BYTES; s.split = KIND == 0 ? SGX_STORE_SPLIT_DEFAULT : 0;
+    const sgx_store_policy pol = sgx_store_policy_multi_step(&s);
+    p.nt_stores = pol.nt_stores; p.plain_lines = (int16_t)(KIND == 0 ? pol.plain_lines : 0);
+    const int now[4] = {n_sets, p.nt_stores, p.plain_lines, s.wg_per_cu};
+    if (h->policy_debug && memcmp(now, h->policy_printed, sizeof(now)) != 0) {
+        memcpy(h->policy_printed, now, sizeof(now));
+        fprintf(stderr, "sgx store policy: kind %d games %lld sets %d cus %d resident_wgs_per_cu %d games_per_wg %d rewrite_set %lld budget %lld -> nt_stores %d plain_lines %d\n",
+                KIND, (long long)s.games, (int)n_sets, s.cus, s.wg_per_cu, s.games_per_wg, (long long)sgx_store_rewrite_set(&s), (long long)s.budget,
+                (int)p.nt_stores, (int)p.plain_lines);
+    }
+    return SGX_OK;
+}
+
 // One launch of steps_kernel.
 static int steps_launch(sgx_env *h, WaveStepsParams &sp, KParams &p, const int32_t *w, hipStream_t stream, bool *ok) {
     const sgx_step_io &io = p.io;
@@ -1014,7 +1078,8 @@ static int steps_launch(sgx_env *h, WaveStepsParams &sp, KParams &p, const int32
     const bool pays = (kind == 0 || kind == 1) && cells >= 36 && cells <= 225 && sp.n_sets >= (cells == 100 ? WSTEPS_MAX_SETS + 1 : 16);
     const bool want_barrier = h->steps_barrier > 0 || (h->steps_barrier < 0 && pays);
     *ok = true;
-    return for_geometry(h, [&](auto r, auto c) {
+    int policy_rc = SGX_OK;
+    const int geo_rc = for_geometry(h, [&](auto r, auto c) {
         constexpr int R = decltype(r)::value, C = decltype(c)::value;
         auto launch = [&](auto kind_c) {
             constexpr int KIND = decltype(kind_c)::value;
@@ -1022,6 +1087,9 @@ static int steps_launch(sgx_env *h, WaveStepsParams &sp, KParams &p, const int32
                 constexpr int VAR = decltype(var)::value;
                 using G = Geo<R, C, VAR>;
                 const unsigned grid = geo_grid<G>(p, w);
+                if constexpr ((KIND == 0 || KIND == 1) && VAR == 0 && (R * C) % 4 == 0) {
+                    if (int rc = steps_policy<R, C, KIND>(h, p, sp.n_sets)) { policy_rc = rc; return; }
+                }
                 sp.k = p;
                 sp.barrier = want_barrier && (p.n_envs - p.env_first) % (G::WPB * G::GPW) == 0;
                 if (h->pool) steps_kernel_pool<R, C, KIND, VAR><<<grid, 64 * G::WPB, 0, stream>>>(WaveStepsParamsPool{sp, make_pool_params(h)});
@@ -1033,6 +1101,7 @@ static int steps_launch(sgx_env *h, WaveStepsParams &sp, KParams &p, const int32
         else if (kind == 4) launch(int_c<4>());
         else launch(int_c<8>());
     });
+    return geo_rc ? geo_rc : policy_rc;
 }
 
 // All n_steps of a rollout call -- output sets first, first + 1, ... round-robin -- in the multi-step launches of one kernel family (SP =
@@ -1165,6 +1234,7 @@ static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_s
                             sp.k = p;
                             sp.k.traj_res_envs = sp.k.traj_out_envs = 0;       // (a step of an sgx_step_traj call: launch_set_step has moved the pointers)
                             sp.k.traj_act_log = nullptr;
+                            sp.k.plain_lines = 0;                              // (a per-step launch: no plain share, SGX_NT_PLAIN_LINES or not)
                             sp.n_steps = sp.n_sets = 1;
                             sp.obs[0] = p.io.obs_dev; sp.fobs[0] = p.io.fobs_dev; sp.mask[0] = p.io.mask_dev;
                             steps_kernel_pool<R, C, KIND, VAR><<<grid, 64 * G::WPB, 0, st>>>(WaveStepsParamsPool{sp, pool_params});

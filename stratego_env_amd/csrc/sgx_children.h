@@ -6,9 +6,8 @@
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// The count: root slot i -> the number of valid moves of its mover (what gen_mask returns).  playout_kernel's shape and geometry (the
-// no-observation kind, one, two or four games per wave), one barrier, the root staged and its mask generated by env_step<PLAY = 5>; no record
-// is written.  k.n_envs = n_roots, k.src_boards / k.src_index = where the roots come from.
+// The count: root slot i -> the number of valid moves of its mover (what gen_mask returns).  The frame (sgx_pool_frame.h) up to its ROOT
+// pass, PLAY_ROOT_COUNT; no record is written.  k.n_envs = n_roots, k.src_boards / k.src_index = where the roots come from.
 // ---------------------------------------------------------------------------------------------
 struct CountParams {
     KParams k;
@@ -26,17 +25,13 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
     __shared__ alignas(16) uint8_t obst_s[G::OBST_BYTES + COMBAT_BYTES];
     const int lane = threadIdx.x & (G::LPG - 1), slot = threadIdx.x / G::LPG;
     const int64_t env = P.env_first + group_of_block(P) * (G::WPB * G::GPW) + slot;
-    const int4 zero4 = make_int4(0, 0, 0, 0);
-    GameInput in{zero4, zero4, zero4, 0, nullptr};
-    if (env < P.n_envs) {
-        in.src = reinterpret_cast<const int4 *>(P.src_boards + (int64_t)(P.src_index ? P.src_index[env] : env) * (int64_t)P.rec_bytes);
-        load_record<G>(P, in.src, lane, in.rq0, in.rq1);
-    }
+    GameInput in = empty_input();
+    if (env < P.n_envs) fetch_root<G>(P, env, lane, in);
     stage_tables<G, KIND>(P, shared, obst_s, threadIdx.x, 64 * G::WPB);
     __syncthreads();   // the one barrier: from here on every wave works on its own games
     if (env >= P.n_envs) return;
-    StepCarry carry{0, 0, 0, 0, 0, 0, 0, 0, false, nullptr, nullptr, nullptr, 0};
-    env_step<R_, C_, KIND, false, false, VAR, 1, false, SGX_KERNARG KParams, PoolParams, 5>(P, LW[slot], shared, obst_s, env, lane, in, nullptr, nullptr, &carry, false);
+    StepCarry carry = pool_carry(0);
+    env_step<R_, C_, KIND, false, false, VAR, 1, false, SGX_KERNARG KParams, PoolParams, PLAY_ROOT_COUNT>(P, LW[slot], shared, obst_s, env, lane, in, nullptr, nullptr, &carry, false);
     if (lane == 0) top->counts[env] = carry.na;
 }
 
@@ -102,16 +97,13 @@ __global__ __launch_bounds__(SCAN_BLOCK) void scan_offsets_kernel(const int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------
-// The children: slot j of dst = child first_child + j.  replay_kernel's shape: the game's lanes find root and rank from `offsets`, the root is
-// staged once, env_step<PLAY = 6> generates its mover's mask and takes the rank-th valid action, env_step<PLAY = 4> applies it as a given
-// action; results and write_record as the replay's.  No atomics, nothing between waves.
+// The children: slot j of dst = child first_child + j.  The frame (sgx_pool_frame.h): the game's lanes find root and rank from `offsets`,
+// PLAY_ROOT_KTH generates the root's mask and takes the rank-th valid action, PLAY_MOVE_GIVEN applies it as a given action.
 // ---------------------------------------------------------------------------------------------
 struct ChildrenArgs {
     const int64_t *offsets;
     int32_t *parent, *action;
-    float *reward;
-    uint8_t *done, *ending_invalid;
-    int8_t *player;
+    ResultOut out;
     int64_t n_roots, first_child;
     int32_t actions_1d;
 };
@@ -167,8 +159,7 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
     const int lane = threadIdx.x & (G::LPG - 1), slot = threadIdx.x / G::LPG;
     const int64_t env = P.env_first + group_of_block(P) * (G::WPB * G::GPW) + slot;     // the slot of dst (k.n_envs = n_children)
     // root, rank and the root's record: all requested before the workgroup stages its tables
-    const int4 zero4 = make_int4(0, 0, 0, 0);
-    GameInput in{zero4, zero4, zero4, 0, nullptr};
+    GameInput in = empty_input();
     int64_t root = -1;
     int rank = 0;
     if (env < P.n_envs) {
@@ -180,8 +171,7 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
             if (k >= 0 && k < 0x7fffffff) {                     // (anything else: offsets that do not belong to these roots)
                 root = i;
                 rank = (int)k;
-                in.src = reinterpret_cast<const int4 *>(P.src_boards + (int64_t)(P.src_index ? P.src_index[i] : i) * (int64_t)P.rec_bytes);
-                load_record<G>(P, in.src, lane, in.rq0, in.rq1);
+                fetch_root<G>(P, i, lane, in);
             }
         }
     }
@@ -189,12 +179,9 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
     __syncthreads();   // from here on every wave works on its own games
     if (env >= P.n_envs) return;
     int32_t *const o_parent = top->ch.parent, *const o_action = top->ch.action;
-    StepCarry carry{0, 0, 0, 0, 0, 0, 0, -1, false, nullptr, nullptr, nullptr, 0};
-    if (root >= 0) {
-        // the root: its record staged, its mover's mask generated, the rank-th valid action taken (-1: the root has no such move)
-        carry.na = rank;
-        env_step<R_, C_, KIND, false, false, VAR, 1, false, SGX_KERNARG KParams, PoolParams, 6>(P, LW[slot], shared, obst_s, env, lane, in, nullptr, nullptr, &carry, false);
-    }
+    StepCarry carry = pool_carry(rank);                         // the rank in, the rank-th valid action out (-1: the root has no such move)
+    if (root >= 0)
+        env_step<R_, C_, KIND, false, false, VAR, 1, false, SGX_KERNARG KParams, PoolParams, PLAY_ROOT_KTH>(P, LW[slot], shared, obst_s, env, lane, in, nullptr, nullptr, &carry, false);
     const int a = carry.na;
     if (root < 0 || a < 0) {                                    // no child: dst's record stays what it was
         if (lane == 0 && o_parent) o_parent[env] = -1;
@@ -202,28 +189,11 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
         return;
     }
     const int qi = (carry.flags & F_PLAYER_M1) ? 1 : 0;         // the root's mover
-    env_step<R_, C_, KIND, false, false, VAR, 2, false, SGX_KERNARG KParams, PoolParams, 4>(P, LW[slot], shared, obst_s, env, lane, in, nullptr, nullptr, &carry, false);
-    // ---- the results: what the step that made the child reports (env_step's rewards / dones)
-    const int flags = carry.flags;
-    const bool over = (flags & F_OVER) != 0, end_invalid = over && (flags & F_END_INVALID);
-    float rew_p1 = 0.f, rew_m1 = 0.f;
-    if (over && !end_invalid) {
-        const int w = (flags & F_WIN_P1) ? 1 : (flags & F_WIN_M1) ? -1 : 0;
-        rew_p1 = w == 0 ? 1e-4f : (float)w;     // impl:838-840
-        rew_m1 = w == 0 ? 1e-4f : (float)-w;
-    }
-    float *const o_reward = top->ch.reward;
-    uint8_t *const o_done = top->ch.done, *const o_end_invalid = top->ch.ending_invalid;
-    int8_t *const o_player = top->ch.player;
+    env_step<R_, C_, KIND, false, false, VAR, 2, false, SGX_KERNARG KParams, PoolParams, PLAY_MOVE_GIVEN>(P, LW[slot], shared, obst_s, env, lane, in, nullptr, nullptr, &carry, false);
     if (lane == 0 && o_parent) o_parent[env] = (int32_t)root;
     if (lane == 0 && o_action) o_action[env] = top->ch.actions_1d ? action_1d_of<G>(a, qi) : a;
-    if (lane < 2 && o_reward) o_reward[2 * env + lane] = lane ? rew_m1 : rew_p1;
-    if (lane == 0 && o_done) o_done[env] = over ? 1 : 0;
-    if (lane == 0 && o_end_invalid) o_end_invalid[env] = end_invalid ? 1 : 0;
-    if (lane == 0 && o_player) o_player[env] = (int8_t)((flags & F_PLAYER_M1) ? -1 : 1);
-    // ---- the child, whole
-    write_record(LW[slot], P.boards + env * (int64_t)P.rec_bytes, P.rec_bytes, make_int4(carry.turn, flags, carry.max_turns, carry.game_no),
-                 make_int4(carry.n_events, carry.rp0, carry.rp1, 0), carry.n_events, lane);
+    store_results(top->ch.out, env, lane, carry.flags);          // what the step that made the child reports
+    write_final_record(LW[slot], P, env, carry, lane);
 }
 
 }  // namespace

@@ -224,12 +224,17 @@ __device__ __forceinline__ GameInput load_game_from(const KP &P, const int4 *src
     }
     return in;
 }
+// game i of a launch that reads ANOTHER pool's records: record src_index[i] (i when NULL) of the source
+template <class KP>
+__device__ __forceinline__ const int8_t *source_record(const KP &P, const int64_t i) {
+    return P.src_boards + (int64_t)(P.src_index ? P.src_index[i] : i) * (int64_t)P.rec_bytes;
+}
 template <class G, bool MAPPED, class KP>
 __device__ __forceinline__ GameInput load_game(const KP &P, const int64_t env, const int lane) {
     if (env >= P.n_envs) { const int4 zero4 = make_int4(0, 0, 0, 0); return GameInput{zero4, zero4, zero4, 0, nullptr}; }
     const int8_t *rec_src = P.boards + env * (int64_t)P.rec_bytes;
     if constexpr (MAPPED)        // sgx_expand: the game comes from another handle's records (functional-API instantiation only)
-        if (P.src_boards) rec_src = P.src_boards + (int64_t)(P.src_index ? P.src_index[env] : env) * (int64_t)P.rec_bytes;
+        if (P.src_boards) rec_src = source_record(P, env);
     return load_game_from<G>(P, reinterpret_cast<const int4 *>(rec_src), env, lane);
 }
 
@@ -280,25 +285,30 @@ __device__ __forceinline__ auto first_of(const StepCarry *carry) {
     if constexpr (PERSIST_ == 3) return static_cast<const StepCarryPool *>(carry)->first;
     else return std::integral_constant<bool, PERSIST_ != 2>{};
 }
-// PLAY (playout_kernel, sgx_playout.h): 0 = none -- every other kernel; 1 = the playout's pass over its ROOT: no move, the record staged, the
-// mover's mask generated and the first action drawn; 2 = one move of the playout.  Both draw the next action with the playout key
-// (pp->draw in the place of game_no, STREAM_PLAYOUT), store nothing -- no per-step result, no next action, no record -- and never auto-reset:
-// the position lives in LDS and *carry until the kernel writes it after its loop.  pp is the playout's PlayParams then.
-// 3 / 4 (replay_kernel, sgx_replay.h): the same two passes with a GIVEN action -- 3 stages the root and plays nothing, 4 applies carry->na
-// exactly as a step applies its action.  Neither draws anything nor needs mask bits: like sgx_expand they only ask whether the next mover
-// has a move (gen_any), and pp is unused.  An invalid action leaves the carry's turn counter where it was: every valid action on an
-// unfinished game advances it (the no-op of a mover without a move included) and a finished game is never stepped, so the caller reads
-// validity from the counter and StepCarry keeps its size.
-// 5 / 6 (count_kernel / children_kernel, sgx_children.h): passes over a ROOT like 1 and 3 -- the record staged, no move, nothing stored, nothing
-// drawn, pp unused -- that generate the mover's mask with its bits and answer through carry->na: 5 leaves the NUMBER of valid moves there
-// (what gen_mask returns: 0 for a finished game and for a mover without a move); 6 takes a rank k from carry->na and leaves the k-th valid
-// action in ascending flat order (kth_valid), or -1 where the root has no more than k moves.  The child itself is PLAY 4 on that action.
+// PLAY: which pass of a pool-to-pool kernel (sgx_pool_frame.h) this call is; PLAY_NONE = every other kernel.  A pass stores nothing -- no
+// per-step result, no next action, no record -- and never auto-resets: the position lives in LDS and *carry until the kernel writes it.
+// A ROOT pass stages the record and plays no move; a MOVE pass applies carry->na exactly as a step applies its action.
+// _DRAW (playout_kernel): the mover's mask is generated and the next action drawn with the playout key (pp->draw in the place of game_no,
+// STREAM_PLAYOUT) into carry->na; pp is the playout's PlayParams.  Every other pass leaves pp unused.
+// _GIVEN (replay_kernel, children_kernel): nothing is drawn and no mask bits are needed -- like sgx_expand the pass only asks whether the
+// next mover has a move (gen_any).  An invalid action leaves the carry's turn counter where it was: every valid action on an unfinished game
+// advances it (the no-op of a mover without a move included) and a finished game is never stepped, so the caller reads validity from the
+// counter and StepCarry keeps its size.
+// PLAY_ROOT_COUNT (count_kernel) leaves the NUMBER of the mover's valid moves in carry->na (what gen_mask returns: 0 for a finished game
+// and for a mover without a move); PLAY_ROOT_KTH (children_kernel) takes a rank k from carry->na and leaves the k-th valid action in
+// ascending flat order (kth_valid), or -1 where the root has no more than k moves.
+enum : int { PLAY_NONE = 0, PLAY_ROOT_DRAW = 1, PLAY_MOVE_DRAW = 2, PLAY_ROOT_GIVEN = 3, PLAY_MOVE_GIVEN = 4, PLAY_ROOT_COUNT = 5, PLAY_ROOT_KTH = 6 };
+constexpr bool play_is_root(const int play) { return play == PLAY_ROOT_DRAW || play == PLAY_ROOT_GIVEN || play == PLAY_ROOT_COUNT || play == PLAY_ROOT_KTH; }
+constexpr bool play_draws(const int play) { return play == PLAY_ROOT_DRAW || play == PLAY_MOVE_DRAW; }
+constexpr bool play_takes_given(const int play) { return play == PLAY_ROOT_GIVEN || play == PLAY_MOVE_GIVEN; }
+constexpr bool play_needs_bits(const int play) { return play != PLAY_NONE && !play_takes_given(play); }
+// KParams::mode of this call (0 = step, 1 = observe): the launch's own, or what the pass is
 template <int PLAY, class KP>
 __device__ __forceinline__ int mode_of(const KP &P) {
-    if constexpr (PLAY != 0) return (PLAY == 1 || PLAY == 3 || PLAY >= 5) ? 1 : 0;
+    if constexpr (PLAY != PLAY_NONE) return play_is_root(PLAY) ? 1 : 0;
     else return P.mode;
 }
-template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, bool POOL = false, class KP = KParams, class PPT = PoolParams, int PLAY = 0>
+template <int R_, int C_, int KIND, bool MAPPED, bool SPLIT = false, int VAR = 0, int PERSIST_ = 0, bool POOL = false, class KP = KParams, class PPT = PoolParams, int PLAY = PLAY_NONE>
 __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsKind<KIND>::NIB_CH> &L, const uint8_t *shared, const uint8_t *obst_s,
                                          const int64_t env, const int lane, const GameInput &in, int8_t *rec_out = nullptr, StepOut *so = nullptr,
                                          StepCarry *carry = nullptr, const bool last = true, const PPT *pp = nullptr) {
@@ -315,7 +325,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     STAMP(0);
     // the step's output tensors: the launch's, or -- one of several steps of a multi-step launch -- this step's output set
     float *const io_obs = PERSIST ? carry->obs : P.io.obs_dev, *const io_fobs = PERSIST ? carry->fobs : P.io.fobs_dev;
-    uint8_t *const io_mask = PLAY ? nullptr : PERSIST ? carry->mask : P.io.mask_dev;
+    uint8_t *const io_mask = PLAY != PLAY_NONE ? nullptr : PERSIST ? carry->mask : P.io.mask_dev;
     // where this step's results go: env, or -- a multi-step launch into a trajectory buffer that keeps every step's results -- the env's
     // place in this step's slot
     int64_t renv = env;
@@ -542,7 +552,8 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
     int qi = player == 1 ? 0 : 1;
     // Launches of the no-observation kind that want neither the mask nor a next action (search expansion, sgx_expand; logic-only steps)
     // only need to know WHETHER the next mover has a move (the opponent-stuck ending): no mask bits, no counts, one cell per ray.
-    const bool want_bits = PLAY >= 5 || (PLAY < 3 && (PLAY != 0 || !NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr)));
+    const bool want_bits = play_needs_bits(PLAY) ||
+                           (PLAY == PLAY_NONE && (!NOOBS || SPLIT || io_mask != nullptr || (P.mode == 0 && P.io.next_actions_dev != nullptr)));
 #ifdef SGX_ABLATE
     if (SGX_ABLATED(P.map_arg, 3)) return;                              // staging only
     int nvalid = gen_mask(L, qi, over, lane, P.map_arg);
@@ -574,7 +585,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
         rew_p1 = w == 0 ? 1e-4f : (float)w;     // impl:838-840
         rew_m1 = w == 0 ? 1e-4f : (float)-w;
     }
-    if (!PLAY && P.mode == 0) {
+    if (PLAY == PLAY_NONE && P.mode == 0) {
         // one store instruction for the rewards (lanes 0/1) and one for the three byte flags (lanes 0..2)
         if (lane < 2 && P.io.reward_dev) P.io.reward_dev[2 * renv + lane] = lane ? rew_m1 : rew_p1;
         uint8_t *fp = lane == 0 ? P.io.done_dev : lane == 1 ? P.io.invalid_action_dev : lane == 2 ? P.io.ending_invalid_dev : nullptr;
@@ -600,7 +611,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
                 // the multi-step kernels of kind 0 (steps_kernel, steps_kernel_pool; partial observation only) give the leading lines of the
                 // observation to plain stores (KParams::plain_lines); every other kernel that plays this step keeps the text it had -- BOTH
                 // mode too, whose instantiations took a VGPR or four bytes of scratch more with a count per observation
-                constexpr bool SPLIT_LINES = PERSIST_ != 0 && PLAY == 0 && KIND == 0;
+                constexpr bool SPLIT_LINES = PERSIST_ != 0 && PLAY == PLAY_NONE && KIND == 0;
                 int plain_lines = 0;
                 if constexpr (SPLIT_LINES) plain_lines = P.plain_lines;
                 if (n_unc == 0) {
@@ -647,7 +658,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
 
     // ---- auto-reset: the finished env starts its next game now
     bool wrote_reset = false;
-    if (!PLAY && P.mode == 0 && ended_now && P.io.auto_reset) {
+    if (PLAY == PLAY_NONE && P.mode == 0 && ended_now && P.io.auto_reset) {
         game_no += 1;
         if constexpr (POOL) {                  // a position of the start pool, with its own clock, mover, recent moves and captures
             const StartScalars st = load_start_record(L, P, *pp, env, game_no, lane);
@@ -673,7 +684,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
 
     STAMP(4);   // results / terminal handling done
     // ---- outputs for the next mover
-    if (!PLAY && lane == 0 && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
+    if (PLAY == PLAY_NONE && lane == 0 && P.io.player_dev) P.io.player_dev[renv] = (int8_t)player;
     if constexpr (SPLIT) {
         if (lane == 0) { so->qi = qi; so->n_events = n_events; so->rp0 = rp0; so->rp1 = rp1; }
     } else {
@@ -709,19 +720,19 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
         if (io_fobs) render(FS{}, true, qi, io_fobs + env * (int64_t)(RC * FS::NCH));
     }
     STAMP(6);   // obs stores issued
-    if constexpr (PLAY == 5) {
+    if constexpr (PLAY == PLAY_ROOT_COUNT) {
         carry->na = nvalid;
-    } else if constexpr (PLAY == 6) {
+    } else if constexpr (PLAY == PLAY_ROOT_KTH) {
         // (kth_valid is run by all lanes of the wave's games alike: the rank is clamped into the mask -- the no-op entry where there is no
         // move -- and the answer dropped where it was not a rank of this root)
         const int k = carry->na;
         const int na = kth_valid(L, max(min(k, nvalid - 1), 0), lane);
         carry->na = (k >= 0 && k < nvalid) ? na : -1;
-    } else if constexpr (PLAY == 1 || PLAY == 2) {
+    } else if constexpr (play_draws(PLAY)) {
         const int total = nvalid == 0 ? 1 : nvalid;
         const uint32_t k = rng_below(sgx_rng(P.seed, (uint64_t)(P.env_id_offset + env), pp->draw, STREAM_PLAYOUT, (uint32_t)turn), (uint32_t)total);
         carry->na = kth_valid(L, (int)k, lane);
-    } else if (PLAY == 0 && P.mode == 0 && P.io.next_actions_dev) {
+    } else if (PLAY == PLAY_NONE && P.mode == 0 && P.io.next_actions_dev) {
         const int total = nvalid == 0 ? 1 : nvalid;
         const uint32_t k = rng_below(sgx_rng(P.seed, (uint64_t)(P.env_id_offset + env), (uint64_t)game_no, STREAM_ACTION, (uint32_t)turn), (uint32_t)total);
         const int na = kth_valid(L, (int)k, lane);

@@ -82,6 +82,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 #include "sgx_mask.h"
 #include "sgx_setup.h"
 #include "sgx_step.h"
+#include "sgx_pool_frame.h"
 #include "sgx_playout.h"
 #include "sgx_replay.h"
 #include "sgx_children.h"
@@ -2102,37 +2103,91 @@ SGX_API int sgx_copy_envs(sgx_env *dst, const int32_t *dst_index_dev, sgx_env *s
     return SGX_OK;
 }
 
+namespace {
+// Where the roots of a pool-to-pool call come from (sgx_expand, sgx_determinize, sgx_playout, sgx_replay, sgx_expand_all): slot i of the
+// launch reads record src_index[i] (i when NULL) of src, so src is dst's variant on dst's device and, without an index, has the `needed`
+// (`needed_name`) records.  Inside one pool a wave would read a record that another wave of the same launch rewrites -- through an index (a
+// gather or a permutation) that silently mixes roots and results; the identity call is safe where slot i is written from record i alone (a
+// wave holds its whole record in LDS before it writes): `in_place_ok`.
+int check_root_source(const char *fn, const sgx_env *dst, const sgx_env *src, const int32_t *src_index_dev, int64_t needed, const char *needed_name, bool in_place_ok = true) {
+    auto refuse = [&](const char *what) { return fail(SGX_EINVAL, "%s", (std::string(fn) + ": " + what).c_str()); };
+    if (same_variant(dst, src) != SGX_OK) return refuse(g_last_error.c_str());
+    if (!src_index_dev && src->n_envs < needed) return refuse((std::string("without src_index_dev the source handle needs at least as many envs as ") + needed_name).c_str());
+    if (src == dst && !in_place_ok) return refuse("src == dst (the results would overwrite the roots); use a second handle as dst");
+    if (src == dst && src_index_dev) return refuse("src == dst with an index array would race; use a second handle as dst");
+    return SGX_OK;
+}
+// The kernels that play from a record into dst's pool never restart a game
+int refuse_start_pool(const char *fn, const sgx_env *dst) {
+    if (!dst->pool) return SGX_OK;
+    return fail(SGX_EINVAL, "%s", (std::string(fn) + ": dst has a start pool set (this call never restarts a game); clear it or use another handle as dst").c_str());
+}
+
+// The KParams of a pool-to-pool launch: dst's, the roots from src (io all NULL / 0: spatial actions in the mover's perspective, no
+// auto-reset, no per-step output)
+KParams pool_params(const sgx_env *dst, const sgx_env *src, const int32_t *src_index_dev, int mode) {
+    KParams p = make_params(dst);
+    p.mode = mode;
+    p.src_boards = src->boards;
+    p.src_index = src_index_dev;
+    return p;
+}
+template <class IO>
+ResultOut result_out(const IO &io) { return ResultOut{io.reward_dev, io.done_dev, io.ending_invalid_dev, io.player_dev}; }
+
+// One launch of a pool-to-pool kernel (sgx_pool_frame.h) over sp.k's envs: the geometry of the logic-only launches.  K names the kernel
+// template: K::kernel<R, C, VAR>() is the instantiation.
+struct PlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_kernel<R, C, VAR>; } };
+struct ReplayK { template <int R, int C, int VAR> static auto kernel() { return &replay_kernel<R, C, VAR>; } };
+struct CountK { template <int R, int C, int VAR> static auto kernel() { return &count_kernel<R, C, VAR>; } };
+struct ChildrenK { template <int R, int C, int VAR> static auto kernel() { return &children_kernel<R, C, VAR>; } };
+template <class K, class SP>
+int launch_pool_kernel(const sgx_env *h, SP &sp, void *stream) {
+    int32_t w[8];
+    launch_setup(h, sp.k, 1, w);
+    if (int rc = for_geometry(h, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            with_half_wave<R, C, 8>(h, [&](auto var) {
+                constexpr int VAR = decltype(var)::value;
+                using G = Geo<R, C, VAR>;
+                const unsigned grid = geo_grid<G>(sp.k, w);
+                K::template kernel<R, C, VAR>()<<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
+            });
+        })) return rc;
+    HIP_TRY(hipGetLastError());
+    return SGX_OK;
+}
+
+// handle scratch of at least `elems` elements (hipFree waits for the launches that still read the old one)
+template <class T>
+int grow_scratch(T **buf, int64_t *cap, int64_t elems) {
+    if (*cap >= elems) return SGX_OK;
+    if (*buf) { HIP_TRY(hipFree(*buf)); *buf = nullptr; *cap = 0; }
+    const int64_t want = elems + elems / 2;
+    HIP_TRY(hipMalloc((void **)buf, (size_t)want * sizeof(T)));
+    *cap = want;
+    return SGX_OK;
+}
+}  // namespace
+
 SGX_API int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_step_io *io, void *stream) {
     if (!dst || !src || !io) return fail(SGX_EINVAL, "handle or io is NULL%s");
     if (!io->actions_dev) return fail(SGX_EINVAL, "actions_dev is NULL%s");
-    if (int rc = same_variant(dst, src)) return rc;
-    if (!src_index_dev && src->n_envs < dst->n_envs) return fail(SGX_EINVAL, "without src_index_dev the source handle needs at least as many envs%s");
-    // wave i reads record src_index[i] while another wave of the same launch rewrites that record: in-place expansion through an
-    // index (a gather or a permutation) would silently mix parents and children
-    if (src == dst && src_index_dev)
-        return fail(SGX_EINVAL, "sgx_expand: src == dst with an index array would race; expand into a second handle%s");
+    if (int rc = check_root_source("sgx_expand", dst, src, src_index_dev, dst->n_envs, "dst")) return rc;
     if (io->auto_reset) return fail(SGX_EINVAL, "sgx_expand does not auto-reset%s");
     if (io->fobs_dev || io->final_fobs_dev || (io->flags & SGX_STEP_ORIGINAL_CHANNELS))
         return fail(SGX_EINVAL, "sgx_expand renders the 67-channel partial observation only%s");
     if (int rc = check_io_pointers(dst, *io, "sgx_expand")) return rc;
     if (int rc = check_aligned("sgx_expand", "src_index_dev", src_index_dev, 4)) return rc;
     SGX_ON_DEVICE(dst->device);
-    KParams p = make_params(dst);
-    p.mode = 0;
+    KParams p = pool_params(dst, src, src_index_dev, 0);
     p.io = *io;
-    p.src_boards = src->boards;
-    p.src_index = src_index_dev;
     return launch_step(dst, p, stream);
 }
 
 SGX_API int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer, uint64_t draw, int32_t *hidden_dev, void *stream) {
     if (!dst || !src) return fail(SGX_EINVAL, "handle is NULL%s");
-    if (int rc = same_variant(dst, src)) return rc;
-    if (!src_index_dev && src->n_envs < dst->n_envs) return fail(SGX_EINVAL, "without src_index_dev the source handle needs at least as many envs%s");
-    // wave i reads record src_index[i] while another wave of the same launch rewrites that record (the identity call is safe: a wave holds
-    // its whole record in LDS before it writes)
-    if (src == dst && src_index_dev)
-        return fail(SGX_EINVAL, "sgx_determinize: src == dst with an index array would race; determinize into a second handle%s");
+    if (int rc = check_root_source("sgx_determinize", dst, src, src_index_dev, dst->n_envs, "dst")) return rc;
     if (observer < -1 || observer > 1) return fail(SGX_EINVAL, "sgx_determinize: observer must be 0 (each record's mover), +1 or -1%s");
     if (int rc = check_aligned("sgx_determinize", "src_index_dev", src_index_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_determinize", "hidden_dev", hidden_dev, 4)) return rc;
@@ -2147,55 +2202,23 @@ SGX_API int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index
 
 SGX_API int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io, uint64_t draw, void *stream) {
     if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_playout: handle or io is NULL%s");
-    if (int rc = same_variant(dst, src)) return rc;
-    if (!src_index_dev && src->n_envs < dst->n_envs) return fail(SGX_EINVAL, "without src_index_dev the source handle needs at least as many envs%s");
-    // wave i reads record src_index[i] while another wave of the same launch writes that record (the identity call is safe: a wave holds
-    // its whole record in LDS before it writes)
-    if (src == dst && src_index_dev)
-        return fail(SGX_EINVAL, "sgx_playout: src == dst with an index array would race; play out into a second handle%s");
+    if (int rc = check_root_source("sgx_playout", dst, src, src_index_dev, dst->n_envs, "dst")) return rc;
     if (io->max_steps < 0) return fail(SGX_EINVAL, "sgx_playout: max_steps must be 0 (to the end of the game) or the most moves to play%s");
     if (io->flags != 0) return fail(SGX_EINVAL, "sgx_playout: flags must be 0%s");
-    if (dst->pool) return fail(SGX_EINVAL, "sgx_playout: dst has a start pool set (a playout never restarts a game); clear it or play out into another handle%s");
+    if (int rc = refuse_start_pool("sgx_playout", dst)) return rc;
     if (int rc = check_aligned("sgx_playout", "src_index_dev", src_index_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_playout", "reward_dev", io->reward_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_playout", "length_dev", io->length_dev, 4)) return rc;
     SGX_ON_DEVICE(dst->device);
-    PlayoutParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.k = make_params(dst);           // (io all NULL / 0: spatial actions in the mover's perspective, no auto-reset, no per-step output)
-    sp.k.mode = 0;
-    sp.k.src_boards = src->boards;
-    sp.k.src_index = src_index_dev;
-    sp.play.draw = draw;
-    sp.play.reward = io->reward_dev; sp.play.done = io->done_dev; sp.play.ending_invalid = io->ending_invalid_dev;
-    sp.play.player = io->player_dev; sp.play.length = io->length_dev;
-    sp.play.max_steps = io->max_steps;
-    int32_t w[8];
-    launch_setup(dst, sp.k, 1, w);
-    if (int rc = for_geometry(dst, [&](auto r, auto c) {
-            constexpr int R = decltype(r)::value, C = decltype(c)::value;
-            with_half_wave<R, C, 8>(dst, [&](auto var) {           // the geometry of the logic-only launches
-                constexpr int VAR = decltype(var)::value;
-                using G = Geo<R, C, VAR>;
-                const unsigned grid = geo_grid<G>(sp.k, w);
-                playout_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
-            });
-        })) return rc;
-    HIP_TRY(hipGetLastError());
+    PlayoutParams sp{pool_params(dst, src, src_index_dev, 0), PlayParams{draw, result_out(*io), io->length_dev, io->max_steps}};
+    if (int rc = launch_pool_kernel<PlayoutK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_PLAYOUT;
     return SGX_OK;
 }
 
 SGX_API int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_replay_io *io, void *stream) {
     if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_replay: handle or io is NULL%s");
-    if (dst->device != src->device) return fail(SGX_EINVAL, "sgx_replay: the two handles live on different devices%s");
-    if (memcmp(&dst->cfg, &src->cfg, sizeof(sgx_config)) != 0 || dst->rec_bytes != src->rec_bytes)
-        return fail(SGX_EINVAL, "sgx_replay: the two handles were created for different variants%s");
-    if (!src_index_dev && src->n_envs < dst->n_envs) return fail(SGX_EINVAL, "sgx_replay: without src_index_dev the source handle needs at least as many envs%s");
-    // wave i reads record src_index[i] while another wave of the same launch writes that record (the identity call is safe: a wave holds
-    // its whole record in LDS before it writes)
-    if (src == dst && src_index_dev)
-        return fail(SGX_EINVAL, "sgx_replay: src == dst with an index array would race; replay into a second handle%s");
+    if (int rc = check_root_source("sgx_replay", dst, src, src_index_dev, dst->n_envs, "dst")) return rc;
     if (io->max_len < 0) return fail(SGX_EINVAL, "sgx_replay: max_len must not be negative%s");
     if (io->flags & ~(SGX_REPLAY_SKIP_INVALID | SGX_REPLAY_ACTIONS_1D | SGX_REPLAY_ALLOW_OSCILLATION)) return fail(SGX_EINVAL, "sgx_replay: unknown flag bits%s");
     if (io->game_stride < 0 || io->step_stride < 0) return fail(SGX_EINVAL, "sgx_replay: game_stride and step_stride must not be negative%s");
@@ -2207,7 +2230,7 @@ SGX_API int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
         if (last >= (__int128)io->actions_elems)
             return fail(SGX_EINVAL, "sgx_replay: (N - 1) * game_stride + (max_len - 1) * step_stride reaches past actions_elems%s");
     }
-    if (dst->pool) return fail(SGX_EINVAL, "sgx_replay: dst has a start pool set (a replay never restarts a game); clear it or replay into another handle%s");
+    if (int rc = refuse_start_pool("sgx_replay", dst)) return rc;
     if (int rc = check_aligned("sgx_replay", "src_index_dev", src_index_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_replay", "actions_dev", io->actions_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_replay", "lengths_dev", io->lengths_dev, 4)) return rc;
@@ -2215,47 +2238,15 @@ SGX_API int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
     if (int rc = check_aligned("sgx_replay", "consumed_dev", io->consumed_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_replay", "reward_dev", io->reward_dev, 4)) return rc;
     SGX_ON_DEVICE(dst->device);
-    ReplayParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.k = make_params(dst);           // (io all NULL / 0: no auto-reset, no per-step output; the decode flags follow)
-    sp.k.mode = 0;
-    sp.k.src_boards = src->boards;
-    sp.k.src_index = src_index_dev;
+    ReplayParams sp{pool_params(dst, src, src_index_dev, 0),
+                    ReplayArgs{io->actions_dev, io->lengths_dev, io->applied_dev, io->consumed_dev, io->stop_dev, result_out(*io), io->game_stride, io->step_stride, io->max_len,
+                               (io->flags & SGX_REPLAY_SKIP_INVALID) ? 1 : 0}};
+    // the step's decode flags the replay's flags translate to
     sp.k.io.flags = ((io->flags & SGX_REPLAY_ACTIONS_1D) ? SGX_STEP_ACTIONS_1D : 0) | ((io->flags & SGX_REPLAY_ALLOW_OSCILLATION) ? SGX_STEP_ALLOW_OSCILLATION : 0);
-    sp.rep.actions = io->actions_dev; sp.rep.lengths = io->lengths_dev;
-    sp.rep.applied = io->applied_dev; sp.rep.consumed = io->consumed_dev; sp.rep.stop = io->stop_dev;
-    sp.rep.reward = io->reward_dev; sp.rep.done = io->done_dev; sp.rep.ending_invalid = io->ending_invalid_dev; sp.rep.player = io->player_dev;
-    sp.rep.game_stride = io->game_stride; sp.rep.step_stride = io->step_stride;
-    sp.rep.max_len = io->max_len;
-    sp.rep.skip_invalid = (io->flags & SGX_REPLAY_SKIP_INVALID) ? 1 : 0;
-    int32_t w[8];
-    launch_setup(dst, sp.k, 1, w);
-    if (int rc = for_geometry(dst, [&](auto r, auto c) {
-            constexpr int R = decltype(r)::value, C = decltype(c)::value;
-            with_half_wave<R, C, 8>(dst, [&](auto var) {           // the geometry of the logic-only launches
-                constexpr int VAR = decltype(var)::value;
-                using G = Geo<R, C, VAR>;
-                const unsigned grid = geo_grid<G>(sp.k, w);
-                replay_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
-            });
-        })) return rc;
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_pool_kernel<ReplayK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_REPLAY;
     return SGX_OK;
 }
-
-namespace {
-// handle scratch of at least `elems` elements (hipFree waits for the launches that still read the old one)
-template <class T>
-int grow_scratch(T **buf, int64_t *cap, int64_t elems) {
-    if (*cap >= elems) return SGX_OK;
-    if (*buf) { HIP_TRY(hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    const int64_t want = elems + elems / 2;
-    HIP_TRY(hipMalloc((void **)buf, (size_t)want * sizeof(T)));
-    *cap = want;
-    return SGX_OK;
-}
-}  // namespace
 
 SGX_API int sgx_count_moves(sgx_env *src, const int32_t *src_index_dev, int64_t n_roots, int32_t *counts_dev, int64_t *offsets_dev, void *stream) {
     if (!src) return fail(SGX_EINVAL, "sgx_count_moves: handle is NULL%s");
@@ -2276,26 +2267,9 @@ SGX_API int sgx_count_moves(sgx_env *src, const int32_t *src_index_dev, int64_t 
         counts_dev = src->count_scratch;
     }
     if (int rc = grow_scratch(&src->scan_sums, &src->scan_sums_cap, n_blocks)) return rc;
-    CountParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.k = make_params(src);           // (io all NULL / 0; nothing of the handle is written)
-    sp.k.mode = 1;
+    CountParams sp{pool_params(src, src, src_index_dev, 1), counts_dev};          // (nothing of the handle is written)
     sp.k.n_envs = n_roots;
-    sp.k.src_boards = src->boards;
-    sp.k.src_index = src_index_dev;
-    sp.counts = counts_dev;
-    int32_t w[8];
-    launch_setup(src, sp.k, 1, w);
-    if (int rc = for_geometry(src, [&](auto r, auto c) {
-            constexpr int R = decltype(r)::value, C = decltype(c)::value;
-            with_half_wave<R, C, 8>(src, [&](auto var) {           // the geometry of the logic-only launches
-                constexpr int VAR = decltype(var)::value;
-                using G = Geo<R, C, VAR>;
-                const unsigned grid = geo_grid<G>(sp.k, w);
-                count_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
-            });
-        })) return rc;
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_pool_kernel<CountK>(src, sp, stream)) return rc;
     scan_sums_kernel<<<(unsigned)n_blocks, SCAN_BLOCK, 0, (hipStream_t)stream>>>(counts_dev, src->scan_sums, n_roots);
     scan_bases_kernel<<<1, SCAN_BLOCK, 0, (hipStream_t)stream>>>(src->scan_sums, n_blocks);
     scan_offsets_kernel<<<(unsigned)n_blocks, SCAN_BLOCK, 0, (hipStream_t)stream>>>(counts_dev, src->scan_sums, offsets_dev, n_roots);
@@ -2305,13 +2279,11 @@ SGX_API int sgx_count_moves(sgx_env *src, const int32_t *src_index_dev, int64_t 
 
 SGX_API int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_children_io *io, void *stream) {
     if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_expand_all: handle or io is NULL%s");
-    if (int rc = same_variant(dst, src)) return rc;
-    if (src == dst) return fail(SGX_EINVAL, "sgx_expand_all: src == dst (children would overwrite roots); expand into a second handle%s");
-    if (dst->pool) return fail(SGX_EINVAL, "sgx_expand_all: dst has a start pool set (an expansion never restarts a game); clear it or expand into another handle%s");
     if (io->n_roots < 0 || io->n_roots > 0x7fffffff || io->n_children < 0 || io->first_child < 0)
         return fail(SGX_EINVAL, "sgx_expand_all: n_roots (below 2^31), n_children and first_child must not be negative%s");
+    if (int rc = check_root_source("sgx_expand_all", dst, src, src_index_dev, io->n_roots, "n_roots", false)) return rc;
+    if (int rc = refuse_start_pool("sgx_expand_all", dst)) return rc;
     if (io->n_children > dst->n_envs) return fail(SGX_EINVAL, "sgx_expand_all: n_children exceeds dst's envs%s");
-    if (!src_index_dev && io->n_roots > src->n_envs) return fail(SGX_EINVAL, "sgx_expand_all: without src_index_dev n_roots must not exceed src's envs%s");
     if (io->flags & ~SGX_CHILDREN_ACTIONS_1D) return fail(SGX_EINVAL, "sgx_expand_all: unknown flag bits%s");
     if (!io->offsets_dev) return fail(SGX_EINVAL, "sgx_expand_all: offsets_dev is NULL%s");
     if (int rc = check_aligned("sgx_expand_all", "src_index_dev", src_index_dev, 4)) return rc;
@@ -2322,31 +2294,10 @@ SGX_API int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_
     dst->last_kind = SGX_LAUNCH_CHILDREN;
     if (io->n_children == 0) return SGX_OK;
     SGX_ON_DEVICE(dst->device);
-    ChildrenParams sp;
-    memset(&sp, 0, sizeof(sp));
-    sp.k = make_params(dst);           // (io all NULL / 0: spatial actions in the mover's perspective, no auto-reset, no per-step output)
-    sp.k.mode = 0;
+    ChildrenParams sp{pool_params(dst, src, src_index_dev, 0),
+                      ChildrenArgs{io->offsets_dev, io->parent_dev, io->action_dev, result_out(*io), io->n_roots, io->first_child, (io->flags & SGX_CHILDREN_ACTIONS_1D) ? 1 : 0}};
     sp.k.n_envs = io->n_children;
-    sp.k.src_boards = src->boards;
-    sp.k.src_index = src_index_dev;
-    sp.ch.offsets = io->offsets_dev;
-    sp.ch.parent = io->parent_dev; sp.ch.action = io->action_dev;
-    sp.ch.reward = io->reward_dev; sp.ch.done = io->done_dev; sp.ch.ending_invalid = io->ending_invalid_dev; sp.ch.player = io->player_dev;
-    sp.ch.n_roots = io->n_roots; sp.ch.first_child = io->first_child;
-    sp.ch.actions_1d = (io->flags & SGX_CHILDREN_ACTIONS_1D) ? 1 : 0;
-    int32_t w[8];
-    launch_setup(dst, sp.k, 1, w);
-    if (int rc = for_geometry(dst, [&](auto r, auto c) {
-            constexpr int R = decltype(r)::value, C = decltype(c)::value;
-            with_half_wave<R, C, 8>(dst, [&](auto var) {           // the geometry of the logic-only launches
-                constexpr int VAR = decltype(var)::value;
-                using G = Geo<R, C, VAR>;
-                const unsigned grid = geo_grid<G>(sp.k, w);
-                children_kernel<R, C, VAR><<<grid, 64 * G::WPB, 0, (hipStream_t)stream>>>(sp);
-            });
-        })) return rc;
-    HIP_TRY(hipGetLastError());
-    return SGX_OK;
+    return launch_pool_kernel<ChildrenK>(dst, sp, stream);
 }
 
 SGX_API int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream) {

@@ -514,7 +514,8 @@ def test_general_states_are_reproduced_not_sanitised(name):
 def test_step_states_refuses_outputs_that_alias_its_inputs_while_the_general_pass_is_on():
     """The general-state pass reads the caller's input again after the first pass has written the outputs (round-4 advisor finding):
     stepping in place would redo flagged states from their own successors.  SGX_EINVAL names the way out; with the pass off, in place works
-    and equals the out-of-place result."""
+    and equals the out-of-place result.  sgx_expand's refusals of its source (another variant, too few records without an index,
+    src == dst through an index) are SGX_EINVAL too and leave the pools' records what they were."""
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import BatchedStrategoProceduralEnv
@@ -542,6 +543,26 @@ def test_step_states_refuses_outputs_that_alias_its_inputs_while_the_general_pas
     half = st.view(-1)[st.numel() // 2:]                                                      # a partial overlap is an overlap
     assert vec._L.sgx_step_states(vec._h, st.data_ptr(), pl.data_ptr(), pe.last_sanitised.data_ptr(), io, half.data_ptr(), other_pl.data_ptr(), 2, vec._stream()) != 0
     assert torch.equal(st.cpu(), torch.from_numpy(states))                                    # nothing was launched
+    # sgx_expand refuses a source it cannot take its roots from, host-side (the check it shares with sgx_determinize, sgx_playout,
+    # sgx_replay and sgx_expand_all): SGX_EINVAL with its message, and the pools keep their records
+    from stratego_env_amd.procedural_env import PackedStates
+    m, SGX_EINVAL = 16, -1
+    dst, small, foreign = pe.pack(st[:m], pl[:m]), pe.pack(st[:m // 2], pl[:m // 2]), PackedStates('standard', m)
+    before = [tuple(t.clone() for t in pool.unpack()) for pool in (dst, small)]
+    idx = torch.zeros(m, dtype=torch.int32, device=pe.device)
+    eio = dst._vec._fill_io(a[:m].contiguous(), False, False, False, _lib.STEP_ACTIONS_1D)
+    eio.auto_reset = 0
+    for src, index, words in ((foreign, None, ('different variants',)), (small, None, ('at least as many envs',)),
+                              (dst, idx.data_ptr(), ('sgx_expand', 'race'))):
+        assert dst._vec._L.sgx_expand(dst._vec._h, src._vec._h, index, eio, dst._vec._stream()) == SGX_EINVAL
+        msg = dst._vec._L.sgx_last_error().decode()
+        assert all(w in msg for w in words), msg
+    torch.cuda.synchronize()
+    for pool, (want_s, want_p) in zip((dst, small), before):
+        got_s, got_p = pool.unpack()
+        assert torch.equal(got_s, want_s) and torch.equal(got_p, want_p)
+    for x in (dst, small, foreign):
+        x.close()
     _lib.check(vec._L.sgx_set_general_states(vec._h, 0), vec._L)
     _lib.check(vec._L.sgx_step_states(*args(st, pl)), vec._L)                                 # in place, pass off: fine
     assert torch.equal(st, want) and torch.equal(pl, want_pl)

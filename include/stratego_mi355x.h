@@ -136,6 +136,7 @@ typedef struct sgx_step_io {
  *   sgx_replay                   src_index_dev, actions_dev, lengths_dev, applied_dev, consumed_dev, reward_dev 4; stop_dev, done_dev, ending_invalid_dev, player_dev 1
  *   sgx_count_moves              src_index_dev, counts_dev 4; offsets_dev 16
  *   sgx_expand_all               src_index_dev, parent_dev, action_dev, reward_dev 4; offsets_dev 16; done_dev, ending_invalid_dev, player_dev 1
+ *   sgx_state_keys               src_index_dev 4; keys_dev 8 (16 with SGX_KEYS_WIDE: one 16-byte store per record)
  *   sgx_mem_probe        ptr_dev 1024;   sgx_store_probe   ptr_dev 16
  * Change note: these rejections are new error returns for pointers that were never legal (the stores they guard were issued unchecked
  * before; only sgx_decode_obs and the compact path refused them); no struct or signature changed, so SGX_ABI_VERSION stays. */
@@ -712,6 +713,42 @@ typedef struct sgx_children_io {
     int32_t flags, reserved;
 } sgx_children_io;                /* 7 pointers + 3 int64 + 2 int32 = 88 bytes */
 int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_children_io *io, void *stream);
+
+/* Position keys: one 64-bit key per packed record (two with SGX_KEYS_WIDE), in one launch straight from the record -- what a transposition
+ * table, the node map of ISMCTS, the deduplication of a start pool and "have I seen this root" need, without an unpack to the int64 layers.
+ * Two views: the STATE key is equal exactly when the reference state (its 34 layers) and the mover are equal; the INFORMATION-SET key of
+ * a player is equal exactly when everything that player can see is equal -- both up to a 64-bit collision (2^-64 per pair; the wide key's
+ * second word is an independent hash of the same features).
+ * THE RULE is defined on the reference state, not on the record layout (tests/keys_rule.py restates it in numpy, known answers included):
+ *   sm_fin(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31   (64-bit, the library's finaliser)
+ *   feat(word, slot, value) = sm_fin(SALT[word] + 0x9E3779B97F4A7C15 * (((slot mod 2^32) << 32 | (value mod 2^32)) + 1)),
+ *   SALT = {0x5347584B45595330, 0x5347584B45595331}; value is taken in two's complement.
+ *   For state int64 [34][R][C] (absolute coordinates) with mover `player`: x = the XOR of
+ *     feat(word, l * 1024 + cell, state[l][cell]) over every NON-ZERO entry of every layer l except 2 (obstacles: a constant of the variant),
+ *       5 (the scalars, below) and, for an information-set key, the true-piece layer of the observer's opponent (layer 1 for observer +1,
+ *       layer 0 for observer -1); cell = r * C + c;
+ *     feat(word, 5 * 1024 + i, s_i) for the scalars s_0 .. s_3 = game over [5][0][1], winner [5][0][2], ending invalid [5][1][1], the mover --
+ *       and, unless SGX_KEYS_NO_CLOCK, s_4 = turn count [5][0][0], s_5 = max turns [5][1][0] -- hashed whether zero or not;
+ *     feat(word, 5 * 1024 + 6, observer) for an information-set key (observer = +1 / -1 after view 0 has been resolved to the mover).
+ *   key = sm_fin(x).  Word 0 is the 64-bit key; SGX_KEYS_WIDE adds word 1.
+ * So: with the clock two positions share a state key exactly when layers and mover agree; SGX_KEYS_NO_CLOCK leaves turn count and max turns
+ * out, so transpositions reached in another number of moves match; an information-set key covers the observer's own pieces, both public
+ * layers, the recent-move layers, the capture counts, the never-moved layers, the scalars, the mover and who observes -- every world
+ * sgx_determinize deals for observer p copies those bit for bit and so has the information-set key of its root.  The game number is not in
+ * the reference state and not in the key.  A capture count is hashed as the count: on a variant with more than 8 pieces of a type the
+ * chained events of one (layer, cell) are summed first.  Like sgx_determinize the information-set key follows the tracked state, not the
+ * move history.
+ * keys_dev[i] (keys_dev[2i], keys_dev[2i + 1] with SGX_KEYS_WIDE) = the key of record src_index_dev[i] of src, of record i when the index is
+ * NULL (then n <= src's envs); index entries must be valid records of src, as for sgx_count_moves.  src is only read -- a pool, or a live env
+ * between launches; the call is asynchronous on `stream`, restores the caller's device, launches nothing for n == 0 and leaves
+ * sgx_last_launch_kind alone.  SGX_EINVAL, before anything is launched: a NULL handle or keys_dev, n outside [0, 2^31), without an index
+ * n > src's envs, a view outside {-1, 0, 1, SGX_KEYS_VIEW_STATE}, unknown flag bits, a misaligned pointer (keys_dev 8 bytes, 16 with
+ * SGX_KEYS_WIDE; src_index_dev 4).  Added without a change to an existing struct or signature: SGX_ABI_VERSION stays.
+ * Reference counterpart: none -- hashing state.tobytes() and the player on the host. */
+#define SGX_KEYS_VIEW_STATE 2      /* view: 0 = each record's mover, +1 / -1 = that player (as sgx_determinize's observer), 2 = state key */
+#define SGX_KEYS_NO_CLOCK 1        /* flags: turn count and max turns stay out of the key */
+#define SGX_KEYS_WIDE     2        /* keys_dev is uint64 [n][2]: word 0 and word 1 (a 128-bit key) */
+int sgx_state_keys(sgx_env *src, const int32_t *src_index_dev, int64_t n, int32_t view, int32_t flags, uint64_t *keys_dev, void *stream);
 
 /* Per-env bookkeeping: int32 [N][4] = {turn count, game number, game_over, current player}. */
 int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream);

@@ -86,6 +86,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 #include "sgx_playout.h"
 #include "sgx_replay.h"
 #include "sgx_children.h"
+#include "sgx_keys.h"
 #include "sgx_lane.h"
 #include "sgx_lane_kernel.h"
 #include "sgx_aux_kernels.h"
@@ -2298,6 +2299,31 @@ SGX_API int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_
                       ChildrenArgs{io->offsets_dev, io->parent_dev, io->action_dev, result_out(*io), io->n_roots, io->first_child, (io->flags & SGX_CHILDREN_ACTIONS_1D) ? 1 : 0}};
     sp.k.n_envs = io->n_children;
     return launch_pool_kernel<ChildrenK>(dst, sp, stream);
+}
+
+SGX_API int sgx_state_keys(sgx_env *src, const int32_t *src_index_dev, int64_t n, int32_t view, int32_t flags, uint64_t *keys_dev, void *stream) {
+    if (!src) return fail(SGX_EINVAL, "sgx_state_keys: handle is NULL%s");
+    if (!keys_dev) return fail(SGX_EINVAL, "sgx_state_keys: keys_dev is NULL%s");
+    if (n < 0 || n > 0x7fffffff) return fail(SGX_EINVAL, "sgx_state_keys: n must be in [0, 2^31)%s");
+    if (!src_index_dev && n > src->n_envs) return fail(SGX_EINVAL, "sgx_state_keys: without src_index_dev n must not exceed the handle's envs%s");
+    if (view != SGX_KEYS_VIEW_STATE && (view < -1 || view > 1))
+        return fail(SGX_EINVAL, "sgx_state_keys: view must be 0 (each record's mover), +1, -1 or SGX_KEYS_VIEW_STATE%s");
+    if (flags & ~(SGX_KEYS_NO_CLOCK | SGX_KEYS_WIDE)) return fail(SGX_EINVAL, "sgx_state_keys: unknown flag bits%s");
+    if (int rc = check_aligned("sgx_state_keys", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_state_keys", "keys_dev", keys_dev, (flags & SGX_KEYS_WIDE) ? 16 : 8)) return rc;
+    if (n == 0) return SGX_OK;
+    SGX_ON_DEVICE(src->device);
+    const KParams k = make_params(src);
+    const KeysParams p{src->boards, src_index_dev, keys_dev, n, src->rec_bytes, src->max_events, k.multi_ev, view, flags & SGX_KEYS_NO_CLOCK};
+    if (int rc = for_geometry(src, [&](auto r, auto c) {
+            constexpr int R = decltype(r)::value, C = decltype(c)::value;
+            constexpr int PER_BLOCK = KEYS_THREADS / Geo<R, C>::LPG;                 // records per workgroup
+            const unsigned grid = (unsigned)((n + PER_BLOCK - 1) / PER_BLOCK);
+            if (flags & SGX_KEYS_WIDE) keys_kernel<R, C, true><<<grid, KEYS_THREADS, 0, (hipStream_t)stream>>>(p);
+            else keys_kernel<R, C, false><<<grid, KEYS_THREADS, 0, (hipStream_t)stream>>>(p);
+        })) return rc;
+    HIP_TRY(hipGetLastError());
+    return SGX_OK;
 }
 
 SGX_API int sgx_get_env_info(sgx_env *h, int32_t *info_dev, void *stream) {

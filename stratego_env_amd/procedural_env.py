@@ -481,6 +481,21 @@ class BatchedStrategoProceduralEnv:
         finally:
             src.close()
 
+    def state_keys(self, states, players, observer=None, clock=True, wide=False):
+        """The position key of every state (PackedStates.state_keys: pack -> keys, for callers on the reference layout): int64 [n] ([n, 2]
+        with wide) on the device.  observer=None: the state key, equal exactly when state and player are equal; 0 (each state's `players`
+        entry) / +1 / -1: that player's information-set key; clock=False leaves turn count and max turns out.  The key is that of the state
+        the packed record carries, so a state the import had to alter gets the key of what it was altered to.  Like the other one-call
+        functions that go through `pack` (determinize, playout, replay, expand_all), and for any n: strict=True raises ValueError on such
+        a state, and `last_sanitised` -- batch_size entries, written by the calls that import into the env's own handle -- is left
+        alone; a caller who wants the flags without strict packs the states itself (`pack(...).sanitised`, then PackedStates.state_keys).
+        No reference counterpart."""
+        src = self.pack(states, players)
+        try:
+            return src.state_keys(observer=observer, clock=clock, wide=wide)
+        finally:
+            src.close()
+
     def close(self):
         self._vec.close()
 
@@ -648,6 +663,12 @@ class PackedStates:
         """-> (counts int32 [n], offsets int64 [n + 1]): the valid moves of record index[i] (None: every record in order) and their exclusive
         scan, on the device without a synchronisation (VecStrategoEnv.count_moves)."""
         return self._vec.count_moves(index)
+
+    def state_keys(self, index=None, observer=None, clock=True, wide=False):
+        """-> int64 [n] ([n, 2] with wide): the position key of record index[i] (None: every record in order), on the device without a
+        synchronisation -- the state key (observer=None) or the information-set key of observer 0 (each record's mover) / +1 / -1; clock=False
+        leaves turn count and max turns out (VecStrategoEnv.state_keys)."""
+        return self._vec.state_keys(index, observer=observer, clock=clock, wide=wide)
 
     def expand_all(self, src, src_index=None, offsets=None, first_child=0, n=None, actions_1d=False):
         """All children of the roots src[src_index[i]] (None: every record of src in order), no action list needed: slot j of this pool

@@ -845,6 +845,27 @@ class VecStrategoEnv:
             _lib.check(self._L.sgx_count_moves(self._h, _ptr(idx) if n else None, n, _ptr(counts) if n else None, _ptr(offsets), self._stream()), self._L)
         return counts, offsets
 
+    def state_keys(self, index=None, observer=None, clock=True, wide=False):
+        """One 64-bit position key per game, straight from the packed records in one launch (sgx_state_keys; the rule is in
+        include/stratego_mi355x.h): slot i is game index[i] (int32 [n], any length, repeats allowed; None: every game in order).
+        observer=None: the state key, equal exactly when the reference state and the mover are equal; observer 0 / +1 / -1 (as determinize
+        takes them: each game's mover / that player): the information-set key, equal exactly when everything that player can see is equal --
+        every world determinize deals for an observer keeps that observer's key.  clock=False leaves turn count and max turns out
+        (transpositions reached in another number of moves match); wide=True adds a second, independent word.
+        -> int64 [n] ([n, 2] with wide) on the device, no synchronisation: the key's BIT PATTERN (torch sorts and uniques int64)."""
+        dev = self.device
+        if observer is not None and int(observer) not in (-1, 0, 1):
+            raise ValueError("observer must be None (the state key), 0 (each game's mover), +1 or -1")
+        idx = None if index is None else torch.as_tensor(index).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        n = self.num_envs if idx is None else int(idx.numel())
+        keys = torch.empty((n, 2) if wide else (n,), dtype=torch.int64, device=dev)
+        view = _lib.KEYS_VIEW_STATE if observer is None else int(observer)
+        flags = (0 if clock else _lib.KEYS_NO_CLOCK) | (_lib.KEYS_WIDE if wide else 0)
+        if n:
+            with torch.cuda.device(dev):
+                _lib.check(self._L.sgx_state_keys(self._h, _ptr(idx), n, view, flags, _ptr(keys), self._stream()), self._L)
+        return keys
+
     def sample_valid_actions(self, mask=None, out=None):
         """Uniformly random valid action per env from `mask` (default: the current one) -- maenv:830-834."""
         own = mask is None or mask is self.mask

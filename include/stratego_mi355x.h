@@ -37,7 +37,8 @@ extern "C" {
 #endif
 
 #define SGX_ABI_VERSION 15       /* (sgx_count_moves, sgx_expand_all and sgx_children_io are additions within v15: new entry points and a new
-                                    struct, no existing layout or signature changed) */
+                                    struct, no existing layout or signature changed; sgx_playout_weighted is an addition within v15 too:
+                                    a new entry point on sgx_playout_io as it is) */
 #define SGX_MAX_CELLS 1024       /* rows*cols <= 1024 (largest reference variant: 15x15 = 225; the reference's StrategoProceduralEnv
                                     takes any size, penv:27-36: boards of more than 256 cells use 10-bit cell indices in the record) */
 #define SGX_PO_OBS_CHANNELS 67   /* impl:1332 */
@@ -133,6 +134,8 @@ typedef struct sgx_step_io {
  *   sgx_expand / sgx_copy_envs   src_index_dev, dst_index_dev 4
  *   sgx_determinize              src_index_dev, hidden_dev 4
  *   sgx_playout                  src_index_dev, reward_dev, length_dev 4; done_dev, ending_invalid_dev, player_dev 1
+ *   sgx_playout_weighted         as sgx_playout; `weights` is HOST memory, read before the call returns (any uint16_t alignment): the
+ *                                contract has nothing to add for it
  *   sgx_replay                   src_index_dev, actions_dev, lengths_dev, applied_dev, consumed_dev, reward_dev 4; stop_dev, done_dev, ending_invalid_dev, player_dev 1
  *   sgx_count_moves              src_index_dev, counts_dev 4; offsets_dev 16
  *   sgx_expand_all               src_index_dev, parent_dev, action_dev, reward_dev 4; offsets_dev 16; done_dev, ending_invalid_dev, player_dev 1
@@ -284,6 +287,7 @@ int sgx_set_steps_barrier(sgx_env *h, int32_t mode);
 #define SGX_LAUNCH_PLAYOUT 4     /* sgx_playout: one wave per game, every move of the playout in one launch (set on dst) */
 #define SGX_LAUNCH_REPLAY 5      /* sgx_replay: one wave per game, every entry of the action list in one launch (set on dst) */
 #define SGX_LAUNCH_CHILDREN 6    /* sgx_expand_all: one wave per child, root found from the offsets, mask regenerated, move applied (set on dst) */
+#define SGX_LAUNCH_PLAYOUT_WEIGHTED 7   /* sgx_playout_weighted: sgx_playout's launch with the weighted draw (set on dst) */
 int sgx_last_launch_kind(const sgx_env *h);
 
 /* Shares of the eight XCDs in a launch of sgx_step / sgx_observe.  Under a saturating write stream the odd XCDs of MI355X drain their
@@ -622,6 +626,44 @@ typedef struct sgx_playout_io {
     int32_t  flags;               /* 0 (anything else SGX_EINVAL) */
 } sgx_playout_io;                 /* 5 pointers + 2 int32 = 48 bytes */
 int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io, uint64_t draw, void *stream);
+
+/* Weighted playouts: sgx_playout with a policy.  Move a is drawn with probability proportional to a caller-given weight of (direction,
+ * moving piece, what stands on the target cell) -- attack what you beat, do not attack what beats you, walk forward -- in the same single
+ * launch, with the same key, pool to pool.  THE RULE (tests/weighted_playout_rule.py restates it on the CPU oracle, bit for bit):
+ *   weights: uint16 [4][13][14], every entry in [0, SGX_PLAYOUT_WEIGHT_MAX = 4095], read as weights[dir][t][d].
+ *   For a position that is not over, with mover p: a_0 < ... < a_{n-1} are the set entries of the mover's perspective mask in ascending
+ *   flat order (a = pcell * K + ch): exactly the moves sgx_playout ranks.  For each move:
+ *     dir = which of the four channel blocks the move's ch lies in, in the order of the mask's channels: perspective +r ([0, R-1)), -r
+ *           ([R-1, 2(R-1))), +c ([2(R-1), 2(R-1) + C-1)), -c (the C-1 after that).  Player +1 sets up on rows 0 .. usable_rows-1 and player
+ *           -1 on the opposite rows, and a mover's perspective is the board turned so that its own rows are the low ones: dir 0 is FORWARD,
+ *           towards the opponent's setup rows, for either player; 1 is backward, 2 and 3 sideways.
+ *     t   = the mover's true piece type on the start cell (1..10).
+ *     d   = what stands on the destination.  By default (the public view) the value of the OPPONENT'S PUBLIC LAYER there: 0 = empty,
+ *           1..12 = a revealed type, 13 = a piece the mover has not identified -- what the mover's partial observation shows.  With
+ *           SGX_PLAYOUT_SEE_ALL the opponent's TRUE type there (0..12): the usual choice inside a determinized world.
+ *     w_i = weights[dir][t][d];  W = the sum of the w_i (32-bit: on any board of at most 1,024 cells 4095 x the most valid moves stays
+ *           below 2^32).
+ *   r = rng(dst's seed, env_id_offset + i, draw, STREAM_PLAYOUT = 6, the position's turn): the SAME draw sgx_playout takes.
+ *     n == 0: the no-op, as in sgx_playout.
+ *     W > 0:  x = rng_below(r, W); the move is the first a_i whose inclusive prefix sum w_0 + ... + w_i exceeds x.
+ *     W == 0: k = rng_below(r, n), the k-th valid move, exactly as sgx_playout.
+ *   Everything else is sgx_playout's: the move bound, max_steps, the results, length, the final record, src only read, the in-place call
+ *   without an index.
+ * Two consequences (both tested): a table whose entries are all the same constant c >= 1 plays, bit for bit, the games sgx_playout plays
+ * (floor(floor(h c n / 2^32) / c) = floor(h n / 2^32)); a move of weight 0 is never drawn while another valid move has a weight > 0.
+ * io is sgx_playout_io as it is, io->flags must still be 0.  `weights` is HOST memory (its name carries no _dev and the alignment contract
+ * has nothing to add): it is read before the call returns -- the table travels in the launch's own arguments -- so the caller may change
+ * or free it at once, and two calls on one stream with different tables each play with their own.
+ * SGX_EINVAL, before anything is launched: weights == NULL; an entry above 4095 (the message names the first offender's indices); unknown
+ * policy_flags bits; and everything sgx_playout refuses, under this function's name.  Sets dst's sgx_last_launch_kind to
+ * SGX_LAUNCH_PLAYOUT_WEIGHTED.  An addition within v15: no existing struct or signature changed, SGX_ABI_VERSION stays.
+ * Reference counterpart: none as a playout; the table is what get_heuristic_rewards_from_move(state, player, action,
+ * reward_matrix[moved type, target type]) (impl:852-891) looks up, with a direction added
+ * (stratego_env_amd/playout_policies.py: from_reward_matrix, capture_biased). */
+#define SGX_PLAYOUT_SEE_ALL 1          /* policy_flags: d is the opponent's true type on the target cell, not what the mover has seen of it */
+#define SGX_PLAYOUT_WEIGHT_MAX 4095
+int sgx_playout_weighted(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io,
+                         const uint16_t *weights /* HOST memory, [4][13][14] */, int32_t policy_flags, uint64_t draw, void *stream);
 
 /* Replay: every slot of `dst` becomes a position of `src` advanced by a GIVEN list of actions, all entries in ONE launch -- what a learner
  * that kept start records and the action log of sgx_step_traj does to get back to (game, t), what a search does to re-derive a node from

@@ -299,4 +299,134 @@ __device__ int kth_valid(const Lds<G, NB> &L, int k, int lane) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The weighted draw of sgx_playout_weighted (playout_weighted_kernel): move a is taken with probability proportional to
+// wtab[dir][t][d] -- dir: the block of its channel (gen_mask's order: perspective +r, -r, +c, -c), t: the mover's true type on the start
+// cell, d: what stands on the target cell, the opponent's public layer (B_PO: 0 empty, 1..12 revealed, 13 unknown) or, see_all, its true
+// type.  wtab is the workgroup's LDS copy of the caller's table, uint16 [4][13][14].
+// ---------------------------------------------------------------------------------------------
+constexpr int WT_TYPES = 13, WT_TARGETS = 14, WT_ENTRIES = 4 * WT_TYPES * WT_TARGETS;    // 728 entries, 1,456 bytes
+
+// Step 1.  One lane per ray, as gen_mask walks them (L.plist, L.occ and the bits of L.mbits are what it left for mover qi): the weights of
+// the ray's set bits, summed over the piece's four rays (quad_sum) into wsum[perspective cell] -- an array of CNT_PAD sums that belongs to
+// the calling kernel.  Returns W, the sum over all valid moves (32-bit: 4095 x the moves of a board of 1,024 cells stays far below 2^32).
+template <class G, int NB>
+__device__ __forceinline__ uint32_t weigh_moves(const Lds<G, NB> &L, uint32_t *wsum, const uint16_t *wtab, const int qi, const bool see_all, const int lane) {
+    constexpr int R = G::R, C = G::C, RC = G::RC, K = G::K;
+    constexpr int OCC_OWN = 1, OCC_ENEMY = 2, OCC_OBST = 4;                        // gen_mask's occupancy bits
+    const int8_t *own = L.b[B_PIECES + qi], *there = L.b[(see_all ? B_PIECES : B_PO) + 1 - qi];
+    for (int i = lane; i < G::CNT_PAD; i += G::LPG) wsum[i] = 0;
+    int npieces = 0;                                                               // the length of gen_mask's list of movable pieces
+#pragma unroll
+    for (int cc = 0; cc < G::CPL; ++cc) {
+        const int i = lane + G::LPG * cc;
+        const int t = i < RC ? own[i] : 0;
+        npieces += __popcll(gballot<G>(t != 0 && t != SP_FLAG && t != SP_BOMB));
+    }
+    wave_sync<G>();
+    const int sgn = qi ? -1 : 1;
+    const int nrays = 4 * npieces;
+    uint32_t mine = 0;
+    for (int j0 = 0; j0 < nrays; j0 += G::LPG) {
+        const int j = j0 + lane;
+        const bool act = j < nrays;
+        const int i = act ? L.plist[j >> 2] : 0, d = j & 3;
+        const int t = own[i];
+        const int r = i / C, c = i - r * C;
+        const int pcell = qi ? RC - 1 - i : i;
+        const int avail = d == 0 ? (qi ? r : R - 1 - r) : d == 1 ? (qi ? R - 1 - r : r) : d == 2 ? (qi ? c : C - 1 - c) : (qi ? C - 1 - c : c);
+        const int delta = d == 0 ? sgn * C : d == 1 ? -sgn * C : d == 2 ? sgn : -sgn;
+        const int bit0 = pcell * K + (d == 0 ? 0 : d == 1 ? R - 1 : d == 2 ? 2 * (R - 1) : 2 * (R - 1) + (C - 1)) - 1;
+        const uint16_t *row = wtab + (d * WT_TYPES + t) * WT_TARGETS;
+        int lim = act ? (t == SP_SCOUT ? avail : min(avail, 1)) : 0;
+        int e = i;
+        uint32_t w = 0;
+        for (int k = 1; k < (R > C ? R : C); ++k) {
+            if (!__any(k <= lim)) break;
+            if (k <= lim) {
+                e += delta;
+                const int v = L.occ[e];
+                if (v & (OCC_OWN | OCC_OBST)) {
+                    lim = 0;
+                } else {
+                    const int bit = bit0 + k;                                      // (clear for the cell the two-square rule vetoes)
+                    if ((L.mbits[bit >> 5] >> (bit & 31)) & 1u) w += row[there[e]];
+                    if (v & OCC_ENEMY) lim = 0;
+                }
+            }
+        }
+        w = (uint32_t)quad_sum((int)w);
+        if (act && d == 0) { wsum[pcell] = w; mine += w; }
+    }
+    const uint32_t total = (uint32_t)uni<G>(glane<G>(gscan_incl<G>((int)mine), G::LPG - 1));
+    wave_sync<G>();                                                                // the sums are written: step 2 reads them
+    return total;
+}
+
+// Steps 2 and 3.  x < W: the first valid move in ascending flat order whose inclusive prefix sum of weights exceeds x.  The cell is found
+// by a scan of the cell sums over the game's lanes (kth_valid's walk with sums for counts); inside the cell one lane per channel -- the
+// order there is the channel index, not the order the rays were walked in -- recomputes its move's weight where its bit is set, in slices of
+// LPG channels on boards with more channels than lanes; every slice is visited by all lanes alike (no cross-lane operation under a
+// condition that differs inside a game).
+template <class G, int NB>
+__device__ __forceinline__ int pick_weighted(const Lds<G, NB> &L, const uint32_t *wsum, const uint16_t *wtab, const int qi, const bool see_all, const uint32_t x,
+                                             const int lane) {
+    constexpr int R = G::R, C = G::C, RC = G::RC, K = G::K;
+    const int8_t *own = L.b[B_PIECES + qi], *there = L.b[(see_all ? B_PIECES : B_PO) + 1 - qi];
+    int cell = 0;
+    uint32_t before = 0, run = 0;
+    bool found = false;
+#pragma unroll
+    for (int cc = 0; cc < G::CPL; ++cc) {
+        const uint32_t c0 = wsum[lane + G::LPG * cc];
+        const uint32_t incl = (uint32_t)gscan_incl<G>((int)c0);
+        const unsigned long long hit = gballot<G>(run + incl > x);
+        const int l = hit ? __ffsll((long long)hit) - 1 : 0;
+        const uint32_t excl = (uint32_t)glane<G>((int)(incl - c0), l);
+        if (!found && hit) {
+            cell = G::LPG * cc + l;
+            before = run + excl;
+            found = true;
+        }
+        run += (uint32_t)glane<G>((int)incl, G::LPG - 1);
+    }
+    cell = uni<G>(cell);
+    const uint32_t rem = (uint32_t)uni<G>((int)(x - before));
+    const int i = qi ? RC - 1 - cell : cell;                                       // the start cell in absolute coordinates
+    const int t = own[i];
+    const int sgn = qi ? -1 : 1;
+    int ch = 0;
+    uint32_t run2 = 0;
+    bool got = false;
+    for (int c0 = 0; c0 < K - 1; c0 += G::LPG) {                                   // (channel K - 1 is the no-op: never a move)
+        const int cl = c0 + lane;
+        const int p = cell * K + (cl < K - 1 ? cl : 0);
+        const bool set = cl < K - 1 && ((L.mbits[p >> 5] >> (p & 31)) & 1u) != 0;
+        const int d = cl < R - 1 ? 0 : cl < 2 * (R - 1) ? 1 : cl < 2 * (R - 1) + (C - 1) ? 2 : 3;
+        const int k = cl - (d == 0 ? 0 : d == 1 ? R - 1 : d == 2 ? 2 * (R - 1) : 2 * (R - 1) + (C - 1)) + 1;
+        const int delta = d == 0 ? sgn * C : d == 1 ? -sgn * C : d == 2 ? sgn : -sgn;
+        const int e = set ? i + k * delta : i;                                     // a set bit is a move that stays on the board
+        const uint32_t w = set ? wtab[(d * WT_TYPES + t) * WT_TARGETS + there[e]] : 0u;
+        const uint32_t incl = (uint32_t)gscan_incl<G>((int)w);
+        const unsigned long long hit = gballot<G>(run2 + incl > rem);
+        if (!got && hit) {
+            ch = c0 + __ffsll((long long)hit) - 1;
+            got = true;
+        }
+        run2 += (uint32_t)glane<G>((int)incl, G::LPG - 1);
+    }
+    return cell * K + ch;
+}
+
+// The next action of a weighted playout at the position gen_mask has just left in L for mover qi with nvalid valid moves (0: the no-op bit
+// alone): r is the playout's draw for this position.  W > 0: the move that holds x = rng_below(r, W); W == 0 (every valid move has weight
+// 0, or there is none): the k-th valid move, k = rng_below(r, max(nvalid, 1)), exactly as sgx_playout.
+template <class G, int NB>
+__device__ __forceinline__ int draw_weighted(const Lds<G, NB> &L, uint32_t *wsum, const uint16_t *wtab, const int qi, const bool see_all, const int nvalid,
+                                             const uint64_t r, const int lane) {
+    const uint32_t W = nvalid > 0 ? weigh_moves(L, wsum, wtab, qi, see_all, lane) : 0u;
+    if (W > 0) return pick_weighted(L, wsum, wtab, qi, see_all, rng_below(r, W), lane);
+    return kth_valid(L, (int)rng_below(r, (uint32_t)(nvalid == 0 ? 1 : nvalid)), lane);
+}
+
 }  // namespace

@@ -297,7 +297,10 @@ __device__ __forceinline__ auto first_of(const StepCarry *carry) {
 // PLAY_ROOT_COUNT (count_kernel) leaves the NUMBER of the mover's valid moves in carry->na (what gen_mask returns: 0 for a finished game
 // and for a mover without a move); PLAY_ROOT_KTH (children_kernel) takes a rank k from carry->na and leaves the k-th valid action in
 // ascending flat order (kth_valid), or -1 where the root has no more than k moves.
-enum : int { PLAY_NONE = 0, PLAY_ROOT_DRAW = 1, PLAY_MOVE_DRAW = 2, PLAY_ROOT_GIVEN = 3, PLAY_MOVE_GIVEN = 4, PLAY_ROOT_COUNT = 5, PLAY_ROOT_KTH = 6 };
+// PLAY_MOVE_COUNT (playout_weighted_kernel, with PLAY_ROOT_COUNT as its root pass) applies carry->na like PLAY_MOVE_DRAW and, like
+// PLAY_ROOT_COUNT, draws nothing: it leaves the next mover's mask bits and per-cell counts in LDS and the number of its valid moves in
+// carry->na; the kernel takes the next action from them itself (draw_weighted, sgx_mask.h).
+enum : int { PLAY_NONE = 0, PLAY_ROOT_DRAW = 1, PLAY_MOVE_DRAW = 2, PLAY_ROOT_GIVEN = 3, PLAY_MOVE_GIVEN = 4, PLAY_ROOT_COUNT = 5, PLAY_ROOT_KTH = 6, PLAY_MOVE_COUNT = 7 };
 constexpr bool play_is_root(const int play) { return play == PLAY_ROOT_DRAW || play == PLAY_ROOT_GIVEN || play == PLAY_ROOT_COUNT || play == PLAY_ROOT_KTH; }
 constexpr bool play_draws(const int play) { return play == PLAY_ROOT_DRAW || play == PLAY_MOVE_DRAW; }
 constexpr bool play_takes_given(const int play) { return play == PLAY_ROOT_GIVEN || play == PLAY_MOVE_GIVEN; }
@@ -720,7 +723,7 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
         if (io_fobs) render(FS{}, true, qi, io_fobs + env * (int64_t)(RC * FS::NCH));
     }
     STAMP(6);   // obs stores issued
-    if constexpr (PLAY == PLAY_ROOT_COUNT) {
+    if constexpr (PLAY == PLAY_ROOT_COUNT || PLAY == PLAY_MOVE_COUNT) {
         carry->na = nvalid;
     } else if constexpr (PLAY == PLAY_ROOT_KTH) {
         // (kth_valid is run by all lanes of the wave's games alike: the rank is clamped into the mask -- the no-op entry where there is no

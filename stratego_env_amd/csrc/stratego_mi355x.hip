@@ -2139,6 +2139,7 @@ ResultOut result_out(const IO &io) { return ResultOut{io.reward_dev, io.done_dev
 // One launch of a pool-to-pool kernel (sgx_pool_frame.h) over sp.k's envs: the geometry of the logic-only launches.  K names the kernel
 // template: K::kernel<R, C, VAR>() is the instantiation.
 struct PlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_kernel<R, C, VAR>; } };
+struct WeightedPlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_weighted_kernel<R, C, VAR>; } };
 struct ReplayK { template <int R, int C, int VAR> static auto kernel() { return &replay_kernel<R, C, VAR>; } };
 struct CountK { template <int R, int C, int VAR> static auto kernel() { return &count_kernel<R, C, VAR>; } };
 struct ChildrenK { template <int R, int C, int VAR> static auto kernel() { return &children_kernel<R, C, VAR>; } };
@@ -2214,6 +2215,33 @@ SGX_API int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev
     PlayoutParams sp{pool_params(dst, src, src_index_dev, 0), PlayParams{draw, result_out(*io), io->length_dev, io->max_steps}};
     if (int rc = launch_pool_kernel<PlayoutK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_PLAYOUT;
+    return SGX_OK;
+}
+
+SGX_API int sgx_playout_weighted(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io, const uint16_t *weights, int32_t policy_flags,
+                                 uint64_t draw, void *stream) {
+    // the policy first: what can be said about it needs no handle
+    if (!weights) return fail(SGX_EINVAL, "sgx_playout_weighted: weights is NULL%s");
+    for (int i = 0; i < WT_ENTRIES; ++i)
+        if (weights[i] > SGX_PLAYOUT_WEIGHT_MAX)
+            return fail(SGX_EINVAL, "%s", ("sgx_playout_weighted: weights[" + std::to_string(i / (WT_TYPES * WT_TARGETS)) + "][" + std::to_string(i / WT_TARGETS % WT_TYPES) +
+                                           "][" + std::to_string(i % WT_TARGETS) + "] = " + std::to_string((int)weights[i]) + " exceeds " +
+                                           std::to_string(SGX_PLAYOUT_WEIGHT_MAX)).c_str());
+    if (policy_flags & ~SGX_PLAYOUT_SEE_ALL) return fail(SGX_EINVAL, "sgx_playout_weighted: unknown policy_flags bits%s");
+    if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_playout_weighted: handle or io is NULL%s");
+    if (int rc = check_root_source("sgx_playout_weighted", dst, src, src_index_dev, dst->n_envs, "dst")) return rc;
+    if (io->max_steps < 0) return fail(SGX_EINVAL, "sgx_playout_weighted: max_steps must be 0 (to the end of the game) or the most moves to play%s");
+    if (io->flags != 0) return fail(SGX_EINVAL, "sgx_playout_weighted: flags must be 0%s");
+    if (int rc = refuse_start_pool("sgx_playout_weighted", dst)) return rc;
+    if (int rc = check_aligned("sgx_playout_weighted", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_playout_weighted", "reward_dev", io->reward_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_playout_weighted", "length_dev", io->length_dev, 4)) return rc;
+    SGX_ON_DEVICE(dst->device);
+    WeightedPlayoutParams sp{pool_params(dst, src, src_index_dev, 0), PlayParams{draw, result_out(*io), io->length_dev, io->max_steps},
+                             (policy_flags & SGX_PLAYOUT_SEE_ALL) ? 1 : 0, 0, {}};
+    memcpy(sp.weights, weights, sizeof(sp.weights));       // the table leaves with the launch's arguments: the caller's copy is free again
+    if (int rc = launch_pool_kernel<WeightedPlayoutK>(dst, sp, stream)) return rc;
+    dst->last_kind = SGX_LAUNCH_PLAYOUT_WEIGHTED;
     return SGX_OK;
 }
 

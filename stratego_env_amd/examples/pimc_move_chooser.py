@@ -16,10 +16,12 @@ from stratego_env_amd.procedural_env import PackedStates
 from stratego_env_amd.vec_env import VecStrategoEnv
 
 
-def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0):
+def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see_all=True):
     """env: a live VecStrategoEnv of B games.  -> (actions int64 [B]: the chosen absolute 1-D action per game, -1 where the game is over;
     values float32 [B, action_size]: the mean playout result of every valid root action from the root mover's side, -inf elsewhere).
-    The worlds and the playouts are keyed by (seed, slot, draw): the same arguments give the same choice."""
+    The worlds and the playouts are keyed by (seed, slot, draw): the same arguments give the same choice.
+    weights: None = uniformly random playouts; else a [4, 13, 14] weight table (stratego_env_amd.playout_policies) the playouts draw their
+    moves by; see_all (with weights only): the playout players look at the sampled world's true piece types, as PIMC assumes."""
     B, W, dev = env.num_envs, int(n_worlds), env.device
     dev_index = dev.index
     info = env.env_info()
@@ -43,7 +45,8 @@ def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0):
             children = PackedStates(env.variant, W * M, device=dev_index, seed=seed)
             valid, _ = children.expand(worlds, action.repeat(W).to(torch.int32), parent_index=parent)
             assert bool(valid.all())
-            res = children.playout(children, max_steps=max_steps, draw=draw)          # in place: the children are scratch
+            res = children.playout(children, max_steps=max_steps, draw=draw, weights=weights,
+                                   see_all=see_all and weights is not None)          # in place: the children are scratch
             value = res.value_for(mover[game].repeat(W))
             sums = torch.zeros(B * A, dtype=torch.float32, device=dev)
             sums.index_add_(0, (game * A + action).repeat(W), value)
@@ -62,11 +65,16 @@ def main():
     ap.add_argument('--games', type=int, default=8)
     ap.add_argument('--worlds', type=int, default=4)
     ap.add_argument('--steps', type=int, default=6, help='random moves played before the choice')
+    ap.add_argument('--biased', action='store_true', help='playouts that prefer winning attacks and forward moves (playout_policies.capture_biased)')
     args = ap.parse_args()
     env = VecStrategoEnv(args.version, args.games, seed=1, auto_reset=False)
     env.reset()
     env.rollout_steps(args.steps)
-    actions, values = choose_moves(env, args.worlds)
+    weights = None
+    if args.biased:
+        from stratego_env_amd.playout_policies import capture_biased
+        weights = capture_biased(args.version)
+    actions, values = choose_moves(env, args.worlds, weights=weights)
     for b, a in enumerate(actions.tolist()):
         if a < 0:
             print("game %d: over" % b)

@@ -21,6 +21,7 @@ Every call imports the states it is given.  A caller that asks several questions
 Search callers avoid the 27 KB int64 layout altogether with PackedStates (pack / expand / unpack below).
 """
 import contextlib
+import ctypes as C
 
 import numpy as np
 import torch
@@ -36,6 +37,24 @@ _SWAP_B = [1, 4, 7, 33] + list(range(20, 32))
 
 def _ptr_or_none(t):
     return t.data_ptr() if t is not None else None
+
+
+def playout_weights(weights):
+    """A weight table of a weighted playout as the library takes it: contiguous uint16 [4, 13, 14] on the host, every entry in [0, 4095].
+    `weights`: an array-like of any integer dtype (numpy, or a CPU tensor) of that shape; ValueError for anything else."""
+    if isinstance(weights, torch.Tensor):
+        if weights.is_cuda:
+            raise ValueError("weights is read on the host: pass a numpy array or a CPU tensor")
+        weights = weights.numpy()
+    w = np.asarray(weights)
+    if w.dtype.kind not in 'iu':
+        raise ValueError("weights must have an integer dtype (got %s): round them yourself (playout_policies documents how it rounds)" % w.dtype)
+    if w.shape != _lib.PLAYOUT_WEIGHTS_SHAPE:
+        raise ValueError("weights must have shape [4, 13, 14] = [direction][moving piece][target] (got %s)" % (tuple(w.shape),))
+    if w.size and (int(w.min()) < 0 or int(w.max()) > _lib.PLAYOUT_WEIGHT_MAX):
+        bad = np.argwhere((w < 0) | (w > _lib.PLAYOUT_WEIGHT_MAX))[0]
+        raise ValueError("weights[%d][%d][%d] = %d is outside [0, %d]" % (bad[0], bad[1], bad[2], int(w[tuple(bad)]), _lib.PLAYOUT_WEIGHT_MAX))
+    return np.ascontiguousarray(w, dtype=np.uint16)
 
 
 class BatchedStrategoProceduralEnv:
@@ -409,9 +428,10 @@ class BatchedStrategoProceduralEnv:
         finally:
             src.close()
 
-    def playout(self, states, players, max_steps=0, draw=0, return_states=False):
+    def playout(self, states, players, max_steps=0, draw=0, return_states=False, weights=None, see_all=False):
         """Every state played to the end of its game with uniformly random valid moves (PackedStates.playout: pack -> playout into a scratch
         pool -> unpack when asked, for callers on the reference layout).  max_steps: 0 = to the end, else at most that many moves.
+        weights / see_all: a [4, 13, 14] weight table for the moves instead of uniform draws, as PackedStates.playout takes it.
         -> PlayoutResult (reward [n,2], done, ending_invalid, player, length; value_for(player)); with return_states
         (result, final states int64 [n,34,R,C], their players int8 [n]).  No reference counterpart: the loop of
         examples/basic_game_loop.py run to dones['__all__'], as a function of a state."""
@@ -419,7 +439,7 @@ class BatchedStrategoProceduralEnv:
         try:
             dst = self.new_packed(src.n)
             try:
-                res = dst.playout(src, max_steps=max_steps, draw=draw)
+                res = dst.playout(src, max_steps=max_steps, draw=draw, weights=weights, see_all=see_all)
                 if not return_states:
                     return res
                 final, final_players = dst.unpack()
@@ -623,13 +643,21 @@ class PackedStates:
         vec._next_actions_fresh = False
         return hidden
 
-    def playout(self, src, src_index=None, max_steps=0, draw=0):
+    def playout(self, src, src_index=None, max_steps=0, draw=0, weights=None, see_all=False):
         """Play src[src_index[i]] to the end of its game with uniformly random valid moves, for every slot i of this pool, in one launch
         (sgx_playout; the rule is in include/stratego_mi355x.h): self[i] becomes the final position, `src` stays what it was.  `src`: a
         PackedStates (this pool itself for an in-place call without src_index) or a live VecStrategoEnv of the same variant; max_steps: 0 =
         to the end, else at most that many moves; the moves are keyed by (this pool's seed, its env_id_offset + i, draw, the position's turn),
-        so many slots of one root -- and another `draw` -- play different games.  -> PlayoutResult."""
+        so many slots of one root -- and another `draw` -- play different games.  -> PlayoutResult.
+        weights: None = uniform (exactly the sgx_playout call); else a [4, 13, 14] array-like of integers in [0, 4095] (numpy or a CPU tensor,
+        stratego_env_amd.playout_policies builds them): a move is drawn with probability proportional to weights[direction][moving piece]
+        [what stands on the target cell] (sgx_playout_weighted, with the same key).  The target is what the mover's partial observation
+        shows (0 = empty, 1..12 = a revealed type, 13 = unknown); see_all=True reads the opponent's true type instead (0..12), the usual
+        choice inside a determinized world.  The table is read before the call returns."""
         vec = self._vec
+        table = None if weights is None else playout_weights(weights)
+        if table is None and see_all:
+            raise ValueError("see_all chooses what a weight table is indexed with: pass weights")
         src_vec = src._vec if isinstance(src, PackedStates) else src
         if src_vec is vec and src_index is not None:
             raise ValueError("in-place playouts through src_index would race (a record may be overwritten before it is read): "
@@ -643,8 +671,13 @@ class PackedStates:
         io = _lib.SgxPlayoutIO(res.reward.data_ptr(), res.done.data_ptr(), res.ending_invalid.data_ptr(), res.player.data_ptr(),
                                res.length.data_ptr(), int(max_steps), 0)
         with torch.cuda.device(self.device):
-            _lib.check(vec._L.sgx_playout(vec._h, src_vec._h, None if si is None else si.data_ptr(), io, int(draw) & 0xFFFFFFFFFFFFFFFF,
-                                          vec._stream()), vec._L)
+            if table is None:
+                _lib.check(vec._L.sgx_playout(vec._h, src_vec._h, None if si is None else si.data_ptr(), io, int(draw) & 0xFFFFFFFFFFFFFFFF,
+                                              vec._stream()), vec._L)
+            else:
+                _lib.check(vec._L.sgx_playout_weighted(vec._h, src_vec._h, None if si is None else si.data_ptr(), io,
+                                                       table.ctypes.data_as(C.POINTER(C.c_uint16)), _lib.PLAYOUT_SEE_ALL if see_all else 0,
+                                                       int(draw) & 0xFFFFFFFFFFFFFFFF, vec._stream()), vec._L)
         vec._next_actions_fresh = False
         return res
 

@@ -34,7 +34,10 @@ __device__ __forceinline__ uint32_t choose_weight(float l, float mx, float scale
     return l == mx ? CHOOSE_ONE : w;
 }
 
-// sum over the lanes of the game of a value < 2^25 (a row of <= 256 weights: < 2^31), the same in every lane of the game
+// sum over the lanes of the game of a value <= 2^25 (VEC weights of at most 2^23 each), the same in every lane of the game.  A row of
+// 256 valid actions with equal logits totals EXACTLY 2^31: the int sums below stay within a 16-lane DPP row (<= 2^29) and the four
+// row totals are added as uint32, so nothing wraps; 16 / 32 lanes per game reach 2^29 / 2^30.  (The search's gscan_incl runs over all
+// 64 lanes in int and is read back as uint32: its last lane may be 2^31 as a bit pattern, which is what the cast yields.)
 template <class G>
 __device__ __forceinline__ uint32_t gsum(uint32_t c) {
     if constexpr (G::LPG == 64) {
@@ -168,6 +171,9 @@ __global__ __launch_bounds__(256) void choose_kernel(const KParams P, const floa
     uint32_t w[VEC], c = 0;
 #pragma unroll
     for (int e = 0; e < VEC; ++e) { w[e] = choose_weight(v[e], mx, scale); c += w[e]; }
+#ifdef SGX_MUTANT_CHOOSE_BEFORE   // tools/mutant_check.sh: on the VEC 4 path without the register cache the pick restarts in its row (arithmetic only: jr stands)
+    if constexpr (VEC == 4 && !CG::CACHE) before = 0;
+#endif
     const unsigned long long incl = before + (unsigned long long)(uint32_t)gscan_incl<G>((int)c);
     const unsigned long long hit = gballot<G>(incl > target);
     const int l = __ffsll((long long)hit) - 1;                         // (hit != 0: the row's total exceeds target - before)

@@ -33,6 +33,30 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def check_choose_tensors(num_envs, n_actions, mask_words, device, mask, out):
+    """What choose_actions() requires of `mask` and `out` before their addresses go to the library, on plain descriptions so that it
+    needs no handle: mask / out = (dtype, device, numel, is_contiguous).  mask: uint8 / bool bytes [N, NA] or int32 words
+    [N, mask_words] (the bit mask of a compact step); out: int32 [N]; both contiguous and on `device`.  -> True for a bit mask;
+    ValueError otherwise."""
+    for what, (dtype, dev, numel, contiguous) in (('mask', mask), ('out', out)):
+        if dev != device:
+            raise ValueError("choose_actions: %s is on %s, the env on %s" % (what, dev, device))
+        if not contiguous:
+            raise ValueError("choose_actions: %s must be contiguous" % what)
+    bits = mask[0] == torch.int32
+    if not bits and mask[0] not in (torch.uint8, torch.bool):
+        raise ValueError("choose_actions: mask must be uint8 / bool bytes or the int32 bit mask of a compact step, not %s" % (mask[0],))
+    want = num_envs * (mask_words if bits else n_actions)
+    if mask[2] != want:
+        raise ValueError("choose_actions: mask holds %d elements, num_envs x %s is %d"
+                         % (mask[2], 'compact_mask_words' if bits else 'rows x columns x ways_to_move', want))
+    if out[0] != torch.int32:
+        raise ValueError("choose_actions: out must be int32, not %s" % (out[0],))
+    if out[2] != num_envs:
+        raise ValueError("choose_actions: out holds %d entries for %d envs" % (out[2], num_envs))
+    return bits
+
+
 class _OutputsOwner:
     """One sgx_alloc_outputs allocation.  It is freed when the LAST reference goes: the env holds one, and so does every tensor
     that views the buffers (torch keeps the object behind __cuda_array_interface__ alive as long as the tensor's storage), so a
@@ -746,7 +770,8 @@ class VecStrategoEnv:
         policy.  temperature 0 = argmax.  The draw is keyed by (seed, global env id, game, turn) like the fused sampler's, and with equal
         logits it is that sampler's action.  Weights are 2^23 fixed point: an action less than 2^-23 as likely as the most likely one is
         never drawn; an env whose valid actions ALL have -inf / NaN logits (or whose mask is empty) gets -1, which step() would flag as
-        an invalid action.  -> int32 [N] (`out` or next_actions: ready for step())."""
+        an invalid action.  `mask` and `out` go to the library as they are: a tensor on another device, not contiguous, of another dtype
+        or size is a ValueError before anything is launched (check_choose_tensors).  -> int32 [N] (`out` or next_actions: ready for step())."""
         lg = logits
         if lg.dtype != torch.float32 or lg.device != self.device or not lg.is_contiguous():
             lg = lg.to(device=self.device, dtype=torch.float32).contiguous()
@@ -754,10 +779,12 @@ class VecStrategoEnv:
             raise ValueError("logits must hold num_envs x rows x columns x ways_to_move floats")
         own = mask is None
         mask = self.mask if mask is None else mask
-        bits = mask.dtype == torch.int32
-        if not bits and mask.numel() != lg.numel():
-            raise ValueError("mask must be uint8 [N, R, C, K] (or the int32 bit mask of a compact step)")
         out = self.next_actions if out is None else out
+        words = 0
+        if mask.dtype == torch.int32:
+            words = self.compact_mask_words if self.compact else int(self._L.sgx_compact_mask_words(self._h))
+        bits = check_choose_tensors(self.num_envs, self.R * self.Cc * self.K, words, self.device,
+                                    *((t.dtype, t.device, t.numel(), t.is_contiguous()) for t in (mask, out)))
         with torch.cuda.device(self.device):
             _lib.check(self._L.sgx_choose_actions(self._h, _ptr(lg), _ptr(mask), C.c_float(float(temperature)),
                                                   _lib.STEP_COMPACT_MASK if bits else 0, _ptr(out), self._stream()), self._L)

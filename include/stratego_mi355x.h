@@ -38,7 +38,7 @@ extern "C" {
 
 #define SGX_ABI_VERSION 15       /* (sgx_count_moves, sgx_expand_all and sgx_children_io are additions within v15: new entry points and a new
                                     struct, no existing layout or signature changed; sgx_playout_weighted is an addition within v15 too:
-                                    a new entry point on sgx_playout_io as it is) */
+                                    a new entry point on sgx_playout_io as it is; so is sgx_determinize_weighted) */
 #define SGX_MAX_CELLS 1024       /* rows*cols <= 1024 (largest reference variant: 15x15 = 225; the reference's StrategoProceduralEnv
                                     takes any size, penv:27-36: boards of more than 256 cells use 10-bit cell indices in the record) */
 #define SGX_PO_OBS_CHANNELS 67   /* impl:1332 */
@@ -133,6 +133,8 @@ typedef struct sgx_step_io {
  *   sgx_set_start_index_out   start_index_dev 4
  *   sgx_expand / sgx_copy_envs   src_index_dev, dst_index_dev 4
  *   sgx_determinize              src_index_dev, hidden_dev 4
+ *   sgx_determinize_weighted     src_index_dev, hidden_dev, off_belief_dev 4; belief_dev 4 (its rows are read as 2-byte elements; every
+ *                                record's table starts an even number of elements behind it)
  *   sgx_playout                  src_index_dev, reward_dev, length_dev 4; done_dev, ending_invalid_dev, player_dev 1
  *   sgx_playout_weighted         as sgx_playout; `weights` is HOST memory, read before the call returns (any uint16_t alignment): the
  *                                contract has nothing to add for it
@@ -594,6 +596,50 @@ int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const s
  * would race and is SGX_EINVAL, like an observer outside {-1, 0, 1}, a handle of another variant or a misaligned pointer (4 bytes).
  * No reference counterpart. */
 int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer, uint64_t draw, int32_t *hidden_dev, void *stream);
+
+/* Determinization from a belief: sgx_determinize with caller-given weights of (opponent type, cell) in the place of the uniform deal -- a
+ * tracker over the move history, a network or a prior over setups (stratego_env_amd/beliefs.py) says where the opponent's pieces are likely
+ * to stand, and the worlds are drawn accordingly, in the same single launch, pool to pool, with the same key and the same guarantees.
+ * THE RULE (tests/determinize_weighted_rule.py restates it in numpy, bit for bit).  For slot i of dst:
+ *   s = src_index[i] (i when the index is NULL), g = dst's env_id_offset + i.
+ *   opp, H, A, B are exactly those of sgx_determinize: opp = the observer's opponent, H = opp's cells whose public layer says 13, A = the
+ *   cells of H that never moved, B = the rest; c_t = the number of pieces of true type t on H.
+ *   A flag or a bomb on a cell of B: the record is copied unchanged, hidden = -1, off_belief = 0.
+ *   Tb = belief_dev + s * belief_stride (in uint16 elements; belief_stride == 0: one table for all records).  A table is uint16
+ *   [2][12][cells]: [opp's player index: 0 = player +1, 1 = player -1, as the record's layers are][t - 1 for t = 1..12][ABSOLUTE cell].
+ *   w(t, c) = min(Tb[(opp * 12 + t - 1) * cells + c], SGX_BELIEF_WEIGHT_MAX = 4095).  The clamp is part of the rule: the table is device
+ *   memory, which the host cannot range-check.
+ *   The types are dealt in the order 11 (flag), 12 (bomb), 10, 9, ..., 1; type t has c_t instances, one after the other; a counter
+ *   j = 0, 1, ... runs over all instances of the deal.  The order is a function of the public multiset of hidden types alone, never of
+ *   where the pieces truly stand.  free = H.  For the instance of type t with counter j:
+ *     the candidates c_0 < ... < c_{m-1} are the cells of free that lie in A when t is 11 or 12, else all cells of free, ascending;
+ *     W = the sum of the w(t, c_k) (32-bit: 1,024 cells x 4,095);
+ *     r = rng(dst's seed, g, draw, STREAM_DETERMINIZE_WEIGHTED = 7, j) with the library's counter RNG;
+ *     W > 0:  x = rng_below(r, W); the cell is the first c_k whose inclusive prefix sum w(t, c_0) + ... + w(t, c_k) exceeds x -- the
+ *             sampler of sgx_playout_weighted;
+ *     W == 0: k = rng_below(r, m), the cell is c_k, and off_belief counts one more;
+ *     pieces[opp][cell] = t, and the cell leaves free.
+ *   m >= 1 at every draw: the immovable types come first and go to A only, |I| <= |A| in a record that is not refused, and afterwards as many
+ *   cells are free as instances remain -- dealing by type instance cannot dead-end, whatever the weights.
+ *   hidden = |H|; off_belief = the number of instances that landed on a cell whose weight for their type is 0 (a caller may discard such
+ *   worlds: the belief called them impossible).
+ * Consequences (all tested): only bytes of pieces[opp] change, so the observer's observation, valid-move mask and information-set key
+ * (sgx_state_keys) are what they were; the multiset of hidden types is kept and flags and bombs stay on never-moved cells; a cell of weight
+ * 0 is never taken while a candidate of positive weight exists; a table whose entries are all the same constant c >= 1 samples UNIFORMLY
+ * over the worlds -- the distribution of sgx_determinize, though not its worlds: the algorithm and the RNG stream are others; a table
+ * that is one-hot on the truth returns the source record bit for bit with off_belief = 0.  The weights steer a sequential deal: they are
+ * NOT the marginals of the result (a cell that an earlier type took is gone for the later ones).
+ * STREAM_DETERMINIZE_WEIGHTED is a stream of its own: no existing draw moves.  belief_dev is DEVICE memory, only read.  hidden_dev,
+ * off_belief_dev: int32 [dst's N], each nullable.  src == dst with a NULL index works in place (a record is read whole before it is
+ * written).  SGX_EINVAL, before anything is launched, under this function's name: everything sgx_determinize refuses (handles of other
+ * variants or devices, a NULL index with src smaller than dst, the in-place call with an index, an observer outside {-1, 0, 1});
+ * belief_dev == NULL; belief_stride negative, odd, or positive and below 2 * 12 * cells; src_index_dev, belief_dev, hidden_dev or
+ * off_belief_dev not 4-byte aligned.  An addition within v15: no existing struct or signature changed, SGX_ABI_VERSION stays.
+ * No reference counterpart. */
+#define SGX_BELIEF_WEIGHT_MAX 4095
+int sgx_determinize_weighted(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer,
+                             const uint16_t *belief_dev, int64_t belief_stride, uint64_t draw,
+                             int32_t *hidden_dev, int32_t *off_belief_dev, void *stream);
 
 /* Playouts: every slot of `dst` plays a position of `src` to the end of its game with uniformly random valid moves, in ONE launch, and
  * reports who won -- what a determinized-MCTS / ISMCTS / PIMC caller does with a sampled world (sgx_determinize) or an expanded node

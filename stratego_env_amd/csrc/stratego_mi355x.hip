@@ -90,6 +90,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 #include "sgx_lane.h"
 #include "sgx_lane_kernel.h"
 #include "sgx_aux_kernels.h"
+#include "sgx_determinize_weighted.h"
 #include "sgx_choose.h"
 #include "sgx_mem.h"
 
@@ -2198,6 +2199,29 @@ SGX_API int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index
     determinize_kernel<<<(unsigned)((dst->n_envs + 3) / 4), 256, 4 * det_lds_bytes(dst->rec_bytes, cells), (hipStream_t)stream>>>(
         dst->boards, src->boards, src_index_dev, hidden_dev, dst->n_envs, dst->seed, dst->env_id_offset, draw, observer, S, dst->sc_off - 2 * sb, sb,
         dst->sc_off, dst->rec_bytes, cells);
+    HIP_TRY(hipGetLastError());
+    return SGX_OK;
+}
+
+SGX_API int sgx_determinize_weighted(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer, const uint16_t *belief_dev,
+                                     int64_t belief_stride, uint64_t draw, int32_t *hidden_dev, int32_t *off_belief_dev, void *stream) {
+    if (!dst || !src) return fail(SGX_EINVAL, "sgx_determinize_weighted: handle is NULL%s");
+    if (int rc = check_root_source("sgx_determinize_weighted", dst, src, src_index_dev, dst->n_envs, "dst")) return rc;
+    if (observer < -1 || observer > 1) return fail(SGX_EINVAL, "sgx_determinize_weighted: observer must be 0 (each record's mover), +1 or -1%s");
+    if (!belief_dev) return fail(SGX_EINVAL, "sgx_determinize_weighted: belief_dev is NULL%s");
+    const int cells = dst->cfg.rows * dst->cfg.cols, S = (cells + 3) & ~3, sb = (((cells + 7) / 8) + 15) & ~15;
+    const int64_t table = 2 * (int64_t)DETW_TYPES * cells;
+    if (belief_stride < 0 || (belief_stride & 1) || (belief_stride > 0 && belief_stride < table))
+        return fail(SGX_EINVAL, "%s", ("sgx_determinize_weighted: belief_stride must be 0 (one table for all records) or an even number of uint16 elements of at least 2 * 12 * cells = " +
+                                       std::to_string(table) + " (got " + std::to_string(belief_stride) + ")").c_str());
+    if (int rc = check_aligned("sgx_determinize_weighted", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_determinize_weighted", "belief_dev", belief_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_determinize_weighted", "hidden_dev", hidden_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_determinize_weighted", "off_belief_dev", off_belief_dev, 4)) return rc;
+    SGX_ON_DEVICE(dst->device);
+    determinize_weighted_kernel<<<(unsigned)((dst->n_envs + 3) / 4), 256, 4 * detw_lds_bytes(dst->rec_bytes, cells), (hipStream_t)stream>>>(
+        dst->boards, src->boards, src_index_dev, belief_dev, belief_stride, hidden_dev, off_belief_dev, dst->n_envs, dst->seed, dst->env_id_offset, draw,
+        observer, S, dst->sc_off - 2 * sb, sb, dst->sc_off, dst->rec_bytes, cells);
     HIP_TRY(hipGetLastError());
     return SGX_OK;
 }

@@ -1,6 +1,6 @@
 """Perfect-information Monte Carlo move choice for B live games at once, on the device: the loop playouts were built for.
 
-    python -m stratego_env_amd.examples.pimc_move_chooser [--version fives] [--games 8] [--worlds 4] [--steps 6]
+    python -m stratego_env_amd.examples.pimc_move_chooser [--version fives] [--games 8] [--worlds 4] [--steps 6] [--biased] [--setup-prior]
 
 For every game the mover does not see the opponent's piece types.  PIMC samples W worlds that look the same to the mover
 (PackedStates.determinize), tries every valid root action in every world (PackedStates.expand, whose parent_index fans the worlds out over
@@ -16,12 +16,14 @@ from stratego_env_amd.procedural_env import PackedStates
 from stratego_env_amd.vec_env import VecStrategoEnv
 
 
-def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see_all=True):
+def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see_all=True, beliefs=None):
     """env: a live VecStrategoEnv of B games.  -> (actions int64 [B]: the chosen absolute 1-D action per game, -1 where the game is over;
     values float32 [B, action_size]: the mean playout result of every valid root action from the root mover's side, -inf elsewhere).
     The worlds and the playouts are keyed by (seed, slot, draw): the same arguments give the same choice.
     weights: None = uniformly random playouts; else a [4, 13, 14] weight table (stratego_env_amd.playout_policies) the playouts draw their
-    moves by; see_all (with weights only): the playout players look at the sampled world's true piece types, as PIMC assumes."""
+    moves by; see_all (with weights only): the playout players look at the sampled world's true piece types, as PIMC assumes.
+    beliefs: None = worlds sampled uniformly; else a [2, 12, cells] belief table (stratego_env_amd.beliefs; numpy or a device tensor) the
+    hidden pieces are dealt by (PackedStates.determinize(..., beliefs=...))."""
     B, W, dev = env.num_envs, int(n_worlds), env.device
     dev_index = dev.index
     info = env.env_info()
@@ -31,7 +33,10 @@ def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see
     children = None
     try:
         game_of_world = torch.arange(B, dtype=torch.int32, device=dev).repeat(W)
-        worlds.determinize(env, src_index=game_of_world, observer=0, draw=draw)
+        if beliefs is None:
+            worlds.determinize(env, src_index=game_of_world, observer=0, draw=draw)
+        else:
+            worlds.determinize(env, src_index=game_of_world, observer=0, draw=draw, beliefs=beliefs)
         # the mover's valid actions are the same in every world of a game: world 0 speaks for all
         mask = worlds.valid_moves_as_1d_mask()[:B] != 0
         mask &= live[:, None]
@@ -66,6 +71,8 @@ def main():
     ap.add_argument('--worlds', type=int, default=4)
     ap.add_argument('--steps', type=int, default=6, help='random moves played before the choice')
     ap.add_argument('--biased', action='store_true', help='playouts that prefer winning attacks and forward moves (playout_policies.capture_biased)')
+    ap.add_argument('--setup-prior', action='store_true',
+                    help="worlds dealt by where humans place their pieces (beliefs.setup_prior; --version barrage or standard)")
     args = ap.parse_args()
     env = VecStrategoEnv(args.version, args.games, seed=1, auto_reset=False)
     env.reset()
@@ -74,7 +81,11 @@ def main():
     if args.biased:
         from stratego_env_amd.playout_policies import capture_biased
         weights = capture_biased(args.version)
-    actions, values = choose_moves(env, args.worlds, weights=weights)
+    beliefs = None
+    if args.setup_prior:
+        from stratego_env_amd.beliefs import setup_prior
+        beliefs = setup_prior(args.version)
+    actions, values = choose_moves(env, args.worlds, weights=weights, beliefs=beliefs)
     for b, a in enumerate(actions.tolist()):
         if a < 0:
             print("game %d: over" % b)

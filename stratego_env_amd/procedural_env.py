@@ -412,15 +412,20 @@ class BatchedStrategoProceduralEnv:
             raise ValueError("state is not one the packed record can carry (unreachable by play)")
         return out
 
-    def determinize(self, states, players, observer=0, draw=0):
+    def determinize(self, states, players, observer=0, draw=0, beliefs=None, return_off_belief=False, validate=True):
         """One sampled world per state for imperfect-information search: the hidden pieces of the observer's opponent dealt again
         (PackedStates.determinize: pack -> determinize into a scratch pool -> unpack, for callers on the reference layout).
         observer: 0 = each state's `players` entry, +1 / -1 = that player for all.  -> (states int64 [n,34,R,C], hidden int32 [n]);
-        hidden[i] = -1 marks a state with a flag or a bomb on a moved hidden cell, returned unchanged.  No reference counterpart."""
+        hidden[i] = -1 marks a state with a flag or a bomb on a moved hidden cell, returned unchanged.  beliefs / return_off_belief /
+        validate: as PackedStates.determinize takes them (a [2, 12, cells] table for all states or one per state); with
+        return_off_belief -> (states, hidden, off_belief).  No reference counterpart."""
         src = self.pack(states, players)
         try:
             dst = self.new_packed(src.n)
             try:
+                if beliefs is not None or return_off_belief:
+                    res = dst.determinize(src, observer=observer, draw=draw, beliefs=beliefs, return_off_belief=return_off_belief, validate=validate)
+                    return (dst.unpack()[0],) + (tuple(res) if return_off_belief else (res,))
                 hidden = dst.determinize(src, observer=observer, draw=draw)
                 return dst.unpack()[0], hidden
             finally:
@@ -621,7 +626,34 @@ class PackedStates:
         vec._next_actions_fresh = False
         return vec.invalid_action == 0, vec.player
 
-    def determinize(self, src, src_index=None, observer=0, draw=0):
+    def _belief_table(self, beliefs, n_src, validate):
+        """beliefs of `determinize` -> (a contiguous 16-bit device tensor, the stride between two records' tables in elements: 0 = shared)."""
+        v = self._vec.variant
+        cells = v.rows * v.columns
+        b = beliefs
+        if isinstance(b, np.ndarray):
+            b = torch.from_numpy(b.astype(np.int32) if b.dtype == np.uint16 else b)
+        if not isinstance(b, torch.Tensor) or b.is_floating_point() or b.is_complex() or b.dtype == torch.bool:
+            raise ValueError("beliefs must be an integer tensor (stratego_env_amd.beliefs builds tables and documents how it rounds)")
+        b = b.to(self.device).contiguous()
+        table = 2 * 12 * cells
+        if tuple(b.shape) == (2, 12, cells):
+            stride = 0
+        elif tuple(b.shape) == (n_src, 2, 12, cells):
+            stride = table
+        else:
+            raise ValueError("beliefs must have shape [2, 12, %d] (one table for all records) or [%d, 2, 12, %d] (one per record of src), got %s"
+                             % (cells, n_src, cells, tuple(b.shape)))
+        sixteen = (torch.int16,) + ((torch.uint16,) if hasattr(torch, 'uint16') else ())
+        if validate:
+            wide = b if b.dtype not in sixteen else b.view(torch.int16).to(torch.int32) & 0xFFFF
+            if bool(((wide < 0) | (wide > _lib.BELIEF_WEIGHT_MAX)).any()):                  # (the one synchronisation)
+                raise ValueError("beliefs must lie in [0, %d]" % _lib.BELIEF_WEIGHT_MAX)
+        if b.dtype not in sixteen:
+            b = b.to(torch.int16)                                   # (the low 16 bits: the library reads them as uint16)
+        return b, stride
+
+    def determinize(self, src, src_index=None, observer=0, draw=0, beliefs=None, return_off_belief=False, validate=True):
         """Sample a world the observer cannot tell from the real one into every slot i of this pool: self[i] = src[src_index[i]] with the
         hidden pieces of the observer's opponent (its pieces the public board shows as unknown) dealt again, uniformly over all assignments
         that keep the flag and the bombs on never-moved cells.  Everything else of the record -- and so the observer's partial observation and
@@ -629,19 +661,39 @@ class PackedStates:
         VecStrategoEnv of the same variant; observer: 0 = each record's mover, +1 / -1 = that player for all; the shuffle is keyed by
         (this pool's seed, its env_id_offset + i, draw), so another `draw` gives independent worlds of the same roots.
         -> hidden int32 [n]: the number of hidden cells shuffled, -1 where a flag or a bomb sits on a moved hidden cell (play cannot produce
-        that; the record is copied unchanged).  The worlds agree with the record's public layers, not with the full move history."""
+        that; the record is copied unchanged).  The worlds agree with the record's public layers, not with the full move history.
+        beliefs: None = the uniform deal above (exactly the sgx_determinize call); else an integer device tensor [2, 12, cells] (one table
+        for all records) or [src's n, 2, 12, cells] (the table of record src_index[i] for slot i), read as beliefs[owner's player index]
+        [type - 1][absolute cell] with entries in [0, 4095] (stratego_env_amd.beliefs builds them): the hidden types are dealt instance by
+        instance -- flags, bombs, then 10 .. 1 -- each onto a free hidden cell drawn with probability proportional to its weight for the
+        type (sgx_determinize_weighted; the rule is in include/stratego_mi355x.h; another RNG stream, so other worlds than the uniform
+        call's even for a constant table).  The range check costs one synchronisation: validate=False skips it (the library clamps
+        entries to 4095), and a tensor that is int16 already is passed without a copy.  The weights steer the deal, they are not the
+        marginals of the worlds.  return_off_belief (with beliefs): -> (hidden, off_belief int32 [n]), off_belief[i] = how many pieces
+        of world i stand on a cell whose weight for their type is 0 (every candidate weighed 0 at that draw); 0 for a record copied unchanged."""
         vec = self._vec
         src_vec = src._vec if isinstance(src, PackedStates) else src
         if src_vec is vec and src_index is not None:
             raise ValueError("in-place determinization through src_index would race (a record may be overwritten before it is read): "
                              "determinize into another pool")
+        if beliefs is None and return_off_belief:
+            raise ValueError("off_belief counts draws outside a belief: pass beliefs")
         si = None if src_index is None else torch.as_tensor(src_index).to(device=self.device, dtype=torch.int32).reshape(self.n).contiguous()
         hidden = torch.empty((self.n,), dtype=torch.int32, device=self.device)
+        if beliefs is None:
+            with torch.cuda.device(self.device):
+                _lib.check(vec._L.sgx_determinize(vec._h, src_vec._h, None if si is None else si.data_ptr(), int(observer),
+                                                  int(draw) & 0xFFFFFFFFFFFFFFFF, hidden.data_ptr(), vec._stream()), vec._L)
+            vec._next_actions_fresh = False
+            return hidden
+        table, stride = self._belief_table(beliefs, src_vec.num_envs, validate)
+        off = torch.empty((self.n,), dtype=torch.int32, device=self.device) if return_off_belief else None
         with torch.cuda.device(self.device):
-            _lib.check(vec._L.sgx_determinize(vec._h, src_vec._h, None if si is None else si.data_ptr(), int(observer),
-                                              int(draw) & 0xFFFFFFFFFFFFFFFF, hidden.data_ptr(), vec._stream()), vec._L)
+            _lib.check(vec._L.sgx_determinize_weighted(vec._h, src_vec._h, None if si is None else si.data_ptr(), int(observer),
+                                                       table.data_ptr(), stride, int(draw) & 0xFFFFFFFFFFFFFFFF, hidden.data_ptr(),
+                                                       _ptr_or_none(off), vec._stream()), vec._L)
         vec._next_actions_fresh = False
-        return hidden
+        return (hidden, off) if return_off_belief else hidden
 
     def playout(self, src, src_index=None, max_steps=0, draw=0, weights=None, see_all=False):
         """Play src[src_index[i]] to the end of its game with uniformly random valid moves, for every slot i of this pool, in one launch

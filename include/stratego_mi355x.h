@@ -11,6 +11,16 @@
  *     and is asynchronous; the entry points that wait for the device are sgx_create, sgx_destroy,
  *     sgx_set_setup_table, sgx_set_start_pool, sgx_time_observe, sgx_mem_probe, sgx_store_probe, sgx_step_sync, sgx_host_free, sgx_alloc_outputs and
  *     sgx_free_outputs;
+ *     every other entry point returns once its work is enqueued, whatever `stream` still holds, and every launch, memset and copy of a
+ *     call that is more than one of them goes to `stream` (sgx_rollout and sgx_step_states with chains > 1 fork streams of the handle off
+ *     `stream` and join them back into it: a consumer on `stream` sees every chain's games, and the chains see what `stream` held before
+ *     the call).  One exception: a call may wait for the device when it is the FIRST of its kind on the handle or when its batch GROWS --
+ *     it then allocates, or frees and reallocates, scratch of the handle (the chain streams of sgx_rollout / sgx_step_states, the flags
+ *     and redo list of sgx_step_states, the count and scan scratch of sgx_count_moves when n_roots grows, the pointer table of
+ *     sgx_step_ring with more than 8 sets when the ring gets longer, the completion word of sgx_step_sync, a kernel's first launch); a
+ *     second call with the same shapes does not wait.  A ring of more than 8 sets may change from call to call, and one handle's ring
+ *     calls may come from different streams, without a host wait: the table's uploads and readers are ordered on the device
+ *     (tests/test_gpu_streams.py holds all of this, entry point by entry point);
  *   - return 0 on success, a negative SGX_E* code on failure (sgx_last_error() has the text);
  *     nothing throws across the ABI; invalid *actions* are not API errors: they are reported per env
  *     in invalid_action[] with that env's state left unchanged (the reference raises ValueError,

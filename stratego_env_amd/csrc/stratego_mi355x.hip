@@ -142,8 +142,10 @@ struct sgx_env {
     int multi_step_wave;         // SGX_MULTI_STEP_WAVE: the multi-step launch of the wave-per-game kernels (steps_kernel) too
     int steps_barrier;           // sgx_set_steps_barrier / SGX_STEPS_BARRIER: -1 auto (long rings that render float32 observations: steps_kernel), 0 never, 1 always
     int half_wave;               // SGX_HALF_WAVE: launches without an observation play two games per wave where the board allows it (Geo<R, C, 2>)
-    // sgx_step_ring with more output sets than fit the kernel arguments: the sets' pointers in a device table (filled through a pinned host
-    // copy; the event guards the staging buffer against being rewritten before the previous upload has run)
+    // sgx_step_ring with more output sets than fit the kernel arguments: the sets' pointers in a device table, written by ring_table_kernel
+    // from its own launch arguments (no staging buffer, so no upload ever waits on the host).  ring_tab_host is a plain host mirror of what
+    // the table holds; ring_tab_ev is recorded behind every upload AND behind every launch that reads the table, on ring_tab_stream: whoever
+    // touches the table next from another stream waits for it on the device.
     void **ring_tab_dev, **ring_tab_host;
     int ring_tab_cap, ring_tab_n;
     hipEvent_t ring_tab_ev;
@@ -537,7 +539,7 @@ SGX_API int sgx_destroy(sgx_env *h) {
     if (h->san_flags) (void)hipFree(h->san_flags);
     if (h->redo_list) (void)hipFree(h->redo_list);
     if (h->ring_tab_dev) (void)hipFree(h->ring_tab_dev);
-    if (h->ring_tab_host) (void)hipHostFree(h->ring_tab_host);
+    free(h->ring_tab_host);
     if (h->ring_tab_ev) (void)hipEventDestroy(h->ring_tab_ev);
     if (h->count_scratch) (void)hipFree(h->count_scratch);
     if (h->scan_sums) (void)hipFree(h->scan_sums);
@@ -856,6 +858,15 @@ struct OutSets {
 
 static int launch_step(sgx_env *h, const KParams &p_in, void *stream, int ring_sets = 1, int64_t start_index_off = 0, bool allow_pool = true);
 
+// The stream of an INNER launch of a call that is more than one launch.  Always the caller's -- except in the test-the-tests build
+// -DSGX_MUTANT_NULL_STREAM (tools/mutant_check.sh, off in every shipped build), where the scan of sgx_count_moves' block sums and the
+// action-log copy of a single trajectory step go to the NULL stream: tests/test_gpu_streams.py has to notice.
+#ifdef SGX_MUTANT_NULL_STREAM
+#define SGX_INNER_STREAM(stream) ((hipStream_t) nullptr)
+#else
+#define SGX_INNER_STREAM(stream) ((hipStream_t)(stream))
+#endif
+
 // ONE step of a rollout call as a launch of its own, writing output set / slot `set`: what the multi-step launches fall back to (calls
 // they do not cover, the odd step a chunk leaves over).
 static int launch_set_step(sgx_env *h, const KParams &p_in, const OutSets &sets, int32_t set, void *stream) {
@@ -880,26 +891,41 @@ static int launch_set_step(sgx_env *h, const KParams &p_in, const OutSets &sets,
     if (int rc = launch_step(h, p1, stream, sets.n_sets, r)) return rc;        // (r: start_index moves on like the results)
     if (p_in.traj_act_log && io.next_actions_dev)
         HIP_TRY(hipMemcpyAsync(p_in.traj_act_log + set * p_in.traj_out_envs, io.next_actions_dev, (size_t)h->n_envs * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                               (hipStream_t)stream));
+                               SGX_INNER_STREAM(stream)));
     return SGX_OK;
 }
 
 // More separate output sets than the kernel arguments hold (sgx_step_ring with n_sets > 8, e.g. a ring of 64 sets that each came from its own
 // placement search): the pointers of the sets go into a device table -- [obs x n][fobs x n][mask x n] -- that the multi-step kernels read with
-// scalar loads.  Uploaded only when the ring changed; ordered on `stream` before the launch that reads it.
+// scalar loads.  Written only when the ring changed, by launches on `stream` that carry the pointers in their own arguments: the host never
+// waits, whatever the stream still holds.  The table is one per handle and streams may alternate on it: ring_tab_ev orders every upload
+// behind the launches that still read the previous table, and every reader behind the upload (ring_table_done records it).
+#define SGX_RING_TAB_CHUNK 32
+struct RingTabChunk { void *ptr[SGX_RING_TAB_CHUNK]; };
+__global__ void ring_table_kernel(void **__restrict__ tab, const RingTabChunk chunk, const int n) {
+    const int i = (int)threadIdx.x;
+    if (i < n) tab[i] = chunk.ptr[i];
+}
+
 static int upload_ring_table(sgx_env *h, const OutSets &sets, hipStream_t stream, void ***tab_out) {
     const int n = sets.n_sets;
-    if (n > h->ring_tab_cap) {
-        if (h->ring_tab_ev) HIP_TRY(hipEventSynchronize(h->ring_tab_ev));
+    if (n > h->ring_tab_cap) {                                 // (growth: hipFree waits for the launches that still read the old table)
+        void **host = (void **)malloc((size_t)3 * n * sizeof(void *));
+        if (!host) return fail(SGX_ENOMEM, "sgx_step_ring: host allocation failed (ring table)%s");
         if (h->ring_tab_dev) HIP_TRY(hipFree(h->ring_tab_dev));
-        if (h->ring_tab_host) HIP_TRY(hipHostFree(h->ring_tab_host));
-        h->ring_tab_dev = h->ring_tab_host = nullptr;
+        free(h->ring_tab_host);
+        h->ring_tab_dev = nullptr;
+        h->ring_tab_host = host;
         h->ring_tab_cap = h->ring_tab_n = 0;
         HIP_TRY(hipMalloc((void **)&h->ring_tab_dev, (size_t)3 * n * sizeof(void *)));
-        HIP_TRY(hipHostMalloc((void **)&h->ring_tab_host, (size_t)3 * n * sizeof(void *), hipHostMallocDefault));
         h->ring_tab_cap = n;
     }
-    if (!h->ring_tab_ev) HIP_TRY(hipEventCreateWithFlags(&h->ring_tab_ev, hipEventDisableTiming));
+    if (!h->ring_tab_ev) {
+        HIP_TRY(hipEventCreateWithFlags(&h->ring_tab_ev, hipEventDisableTiming));
+        h->ring_tab_stream = stream;                           // (nothing recorded yet: nothing to wait for)
+    }
+    // what other streams did with the table so far -- uploads and reads -- comes first
+    if (h->ring_tab_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, h->ring_tab_ev, 0));
     std::vector<void *> want((size_t)3 * n);
     for (int k = 0; k < n; ++k) {
         want[k] = sets.ios[k].obs_dev;
@@ -908,17 +934,28 @@ static int upload_ring_table(sgx_env *h, const OutSets &sets, hipStream_t stream
     }
     const bool same = h->ring_tab_n == n && memcmp(h->ring_tab_host, want.data(), want.size() * sizeof(void *)) == 0;
     if (!same) {
-        if (h->ring_tab_n) HIP_TRY(hipEventSynchronize(h->ring_tab_ev));          // (the staging buffer's previous upload has run)
+        // (laid out for n sets: a smaller ring after a larger one re-packs the three sections)
+        for (size_t at = 0; at < want.size(); at += SGX_RING_TAB_CHUNK) {
+            RingTabChunk chunk;
+            const int now = (int)(want.size() - at < SGX_RING_TAB_CHUNK ? want.size() - at : SGX_RING_TAB_CHUNK);
+            memset(&chunk, 0, sizeof(chunk));
+            memcpy(chunk.ptr, want.data() + at, (size_t)now * sizeof(void *));
+            ring_table_kernel<<<1, 64, 0, stream>>>(h->ring_tab_dev + at, chunk, now);
+        }
+        HIP_TRY(hipGetLastError());
         memcpy(h->ring_tab_host, want.data(), want.size() * sizeof(void *));
-        // (laid out for capacity n: a smaller ring after a larger one re-packs the three sections)
-        HIP_TRY(hipMemcpyAsync(h->ring_tab_dev, h->ring_tab_host, want.size() * sizeof(void *), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(h->ring_tab_ev, stream));
         h->ring_tab_n = n;
+        HIP_TRY(hipEventRecord(h->ring_tab_ev, stream));       // (should the launch behind it never come, readers elsewhere still find the upload)
         h->ring_tab_stream = stream;
-    } else if (h->ring_tab_stream != stream) {
-        HIP_TRY(hipStreamWaitEvent(stream, h->ring_tab_ev, 0));                     // (uploaded on another stream: order this launch behind it)
     }
     *tab_out = h->ring_tab_dev;
+    return SGX_OK;
+}
+
+// Behind the launches that read the ring table: the next upload, from any stream, waits for them.
+static int ring_table_done(sgx_env *h, hipStream_t stream) {
+    HIP_TRY(hipEventRecord(h->ring_tab_ev, stream));
+    h->ring_tab_stream = stream;
     return SGX_OK;
 }
 
@@ -1158,6 +1195,8 @@ static int multi_step(sgx_env *h, const KParams &p_in, const OutSets &sets, int3
         }
         done += now;
     }
+    if (sp.strided == 2)
+        if (int rc = ring_table_done(h, (hipStream_t)stream)) return rc;
     *launched = true;
     h->last_kind = lane ? SGX_LAUNCH_MULTI_STEP : SGX_LAUNCH_MULTI_STEP_WAVE;
     return SGX_OK;
@@ -2324,7 +2363,7 @@ SGX_API int sgx_count_moves(sgx_env *src, const int32_t *src_index_dev, int64_t 
     sp.k.n_envs = n_roots;
     if (int rc = launch_pool_kernel<CountK>(src, sp, stream)) return rc;
     scan_sums_kernel<<<(unsigned)n_blocks, SCAN_BLOCK, 0, (hipStream_t)stream>>>(counts_dev, src->scan_sums, n_roots);
-    scan_bases_kernel<<<1, SCAN_BLOCK, 0, (hipStream_t)stream>>>(src->scan_sums, n_blocks);
+    scan_bases_kernel<<<1, SCAN_BLOCK, 0, SGX_INNER_STREAM(stream)>>>(src->scan_sums, n_blocks);
     scan_offsets_kernel<<<(unsigned)n_blocks, SCAN_BLOCK, 0, (hipStream_t)stream>>>(counts_dev, src->scan_sums, offsets_dev, n_roots);
     HIP_TRY(hipGetLastError());
     return SGX_OK;

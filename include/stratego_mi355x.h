@@ -9,7 +9,7 @@
  *     (e.g. a torch tensor's data_ptr()); the library owns only its internal state tensor;
  *   - all device work is enqueued on `stream` (a hipStream_t passed as void*, NULL = default stream)
  *     and is asynchronous; the entry points that wait for the device are sgx_create, sgx_destroy,
- *     sgx_set_setup_table, sgx_set_start_pool, sgx_time_observe, sgx_mem_probe, sgx_store_probe, sgx_step_sync, sgx_host_free, sgx_alloc_outputs and
+ *     sgx_set_setup_table, sgx_set_start_pool, sgx_set_leaf_values, sgx_time_observe, sgx_mem_probe, sgx_store_probe, sgx_step_sync, sgx_host_free, sgx_alloc_outputs and
  *     sgx_free_outputs;
  *     every other entry point returns once its work is enqueued, whatever `stream` still holds, and every launch, memset and copy of a
  *     call that is more than one of them goes to `stream` (sgx_rollout and sgx_step_states with chains > 1 fork streams of the handle off
@@ -811,6 +811,37 @@ typedef struct sgx_children_io {
     int32_t flags, reserved;
 } sgx_children_io;                /* 7 pointers + 3 int64 + 2 int32 = 88 bytes */
 int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_children_io *io, void *stream);
+
+/* Leaf values: what a position that is NOT over is worth, by a piece-square table -- so that a playout cut off by max_steps, a replayed
+ * prefix and every child of sgx_expand_all carry an estimate where they reported 0, 0.  A SETTING OF THE dst HANDLE, like sgx_set_start_pool:
+ * sgx_playout, sgx_playout_weighted, sgx_replay and sgx_expand_all pick it up from their dst; sgx_replay with max_len == 0 is the
+ * stand-alone "score this pool" call.  No existing struct or signature changed: SGX_ABI_VERSION stays.
+ * THE RULE is defined on the reference state, not on the record layout (tests/leaf_values_rule.py restates it in numpy, known answers
+ * included).  For state int64 [34][R][C] (absolute coordinates), cells = R * C, cell = r * C + c, and the table T = int16 [2][14][cells]:
+ *   own(p)  = layer 0 for player +1, layer 1 for -1 (true pieces, 1..12);
+ *   pub(p)  = layer 3 for +1, layer 4 for -1 (what p's opponent knows of p's pieces: 1..12 identified, 13 unidentified);
+ *   persp(p, cell) = cell for +1, cells - 1 - cell for -1: the board turned into the owner's perspective, so a table row means "this far
+ *     advanced" for either player;
+ *   mine(p)   = the sum of T[0][t][persp(p, cell)], t = state[own(p)][cell], over the non-zero cells of own(p);
+ *   theirs(p) = the sum of T[1][d][persp(-p, cell)] over the non-zero cells of the layer d is read from: d = state[pub(-p)][cell] (what p
+ *     sees; the default), or with SGX_LEAF_SEE_ALL d = state[own(-p)][cell] (the usual choice inside a determinized world);
+ *     rows T[.][0] and T[0][13] are never read;
+ *   S(p) = mine(p) - theirs(p) in int32 (|S| <= 2 * 1,024 * 32,768);
+ *   v(p) = float32(clamp(S(p), -limit, limit)) / float32(denom): ONE IEEE division of two integers of magnitude <= 2^24.
+ * With a table set on dst, every slot whose reported position is not over gets reward[+1] = v(+1), reward[-1] = v(-1) -- in the public
+ * view each is that player's OWN estimate, not the negative of the other's.  done, ending_invalid, player, length, applied / consumed /
+ * stop, parent / action and the records written are what they are without a table; a finished position reports what it reports without
+ * one (0, 0 for a max-turn ending and an invalid ending, the 1e-4 of a tie included); "no child" slots of sgx_expand_all are still not
+ * written; nothing is drawn.  With no table set every byte of every output is what it was.  sgx_step and all live-env stepping, sgx_expand
+ * and sgx_step_states never use the table.  limit < denom keeps leaf values strictly inside a win's +-1.
+ * table_host is HOST memory, copied into a device buffer the handle owns (freed by sgx_destroy); NULL clears the setting and ignores the
+ * other arguments.  The call WAITS FOR THE DEVICE: launches in flight finish with the table they were launched with, and the old buffer is
+ * freed only then; every later launch takes the new one.  The table is a setting, not game state: sgx_copy_envs, snapshots and start pools
+ * do not carry it.  SGX_EINVAL, before anything is uploaded: a NULL handle, limit or denom outside 1 <= limit <= denom <= 2^24, unknown
+ * flag bits.  Reference counterpart: none -- a Python evaluation of every leaf state on the host. */
+#define SGX_LEAF_SEE_ALL 1             /* flags: the opponent's pieces are valued by their true types, not by what the player has seen of them */
+int sgx_set_leaf_values(sgx_env *h, const int16_t *table_host /* [2][14][cells], NULL = clear */, int32_t limit, int32_t denom, int32_t flags);
+int sgx_leaf_values_set(const sgx_env *h);   /* 1 / 0 */
 
 /* Position keys: one 64-bit key per packed record (two with SGX_KEYS_WIDE), in one launch straight from the record -- what a transposition
  * table, the node map of ISMCTS, the deduplication of a start pool and "have I seen this root" need, without an unpack to the int64 layers.

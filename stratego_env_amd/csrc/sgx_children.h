@@ -110,6 +110,7 @@ struct ChildrenArgs {
 struct ChildrenParams {
     KParams k;
     ChildrenArgs ch;
+    LeafParams leaf;      // read by the LEAF instantiation alone
 };
 
 // The root of child c: the LAST i in [0, n_roots) with offsets[i] <= c (roots without a move share their offset with the next one), found by
@@ -147,7 +148,7 @@ __device__ inline int action_1d_of(const int a, const int qi) {
     return (sr * C + sc) * MPA + ((er != sr) ? er : R + ec);
 }
 
-template <int R_, int C_, int VAR = 0>
+template <int R_, int C_, int VAR = 0, bool LEAF = false>
 __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd<Geo<R_, C_, VAR>, 8>())) void children_kernel(const ChildrenParams SP) {
     using G = Geo<R_, C_, VAR>;
     constexpr int KIND = 8;
@@ -192,7 +193,8 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
     env_step<R_, C_, KIND, false, false, VAR, 2, false, SGX_KERNARG KParams, PoolParams, PLAY_MOVE_GIVEN>(P, LW[slot], shared, obst_s, env, lane, in, nullptr, nullptr, &carry, false);
     if (lane == 0 && o_parent) o_parent[env] = (int32_t)root;
     if (lane == 0 && o_action) o_action[env] = top->ch.actions_1d ? action_1d_of<G>(a, qi) : a;
-    store_results(top->ch.out, env, lane, carry.flags);          // what the step that made the child reports
+    if constexpr (LEAF) store_results_leaf(LW[slot], top->ch.out, top->leaf, env, lane, carry.flags);
+    else store_results(top->ch.out, env, lane, carry.flags);      // what the step that made the child reports
     write_final_record(LW[slot], P, env, carry, lane);
 }
 

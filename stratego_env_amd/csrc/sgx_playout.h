@@ -15,6 +15,7 @@ struct PlayParams {
 struct PlayoutParams {
     KParams k;
     PlayParams play;
+    LeafParams leaf;      // read by the LEAF instantiation alone
 };
 
 // The frame (sgx_pool_frame.h) around the sampler: PLAY_ROOT_DRAW generates the root's mask and draws the first action, then PLAY_MOVE_DRAW
@@ -22,7 +23,7 @@ struct PlayoutParams {
 // The loop is bounded by a COUNT: every applied move advances the turn counter and the max-turn ending fires at turn >= max_turns, so a game
 // that starts at `turn` has at most max(max_turns - turn, 0) + 1 moves left (the + 1: a root at or past its last turn that is not over yet
 // still plays the move that ends it).  A game that were not over after that many moves would be reported like one cut off by max_steps.
-template <int R_, int C_, int VAR = 0>
+template <int R_, int C_, int VAR = 0, bool LEAF = false>
 __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd<Geo<R_, C_, VAR>, 8>())) void playout_kernel(const PlayoutParams SP) {
     using G = Geo<R_, C_, VAR>;
     constexpr int KIND = 8;
@@ -52,7 +53,8 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
         env_step<R_, C_, KIND, false, false, VAR, 2, false, SGX_KERNARG KParams, SGX_KERNARG PlayParams, PLAY_MOVE_DRAW>(tp->k, LW[slot_t], shared, obst_s, env, lane_t, in, nullptr,
                                                                                                                          nullptr, &carry, false, &tp->play);
     }
-    store_results(top->play.out, env, lane, carry.flags);
+    if constexpr (LEAF) store_results_leaf(LW[slot], top->play.out, top->leaf, env, lane, carry.flags);
+    else store_results(top->play.out, env, lane, carry.flags);
     int32_t *const o_length = top->play.length;
     if (lane == 0 && o_length) o_length[env] = t;
     write_final_record(LW[slot], P, env, carry, lane);
@@ -67,6 +69,7 @@ struct WeightedPlayoutParams {
     PlayParams play;
     int32_t see_all, reserved;
     uint16_t weights[WT_ENTRIES];
+    LeafParams leaf;      // read by the LEAF instantiation alone
 };
 static_assert(sizeof(WeightedPlayoutParams) <= 4096 && offsetof(WeightedPlayoutParams, weights) % 4 == 0, "the table travels in the kernel arguments");
 
@@ -82,7 +85,7 @@ constexpr int weighted_waves_per_simd() {
 // (PLAY_ROOT_COUNT / PLAY_MOVE_COUNT: the mask bits stay in LDS, the number of valid moves comes back in the carry) and the kernel draws
 // from what they left.  The workgroup stages the table into LDS with its other shared tables, before its one barrier; the per-cell weight
 // sums are an LDS array of this kernel, one row per game.
-template <int R_, int C_, int VAR = 0>
+template <int R_, int C_, int VAR = 0, bool LEAF = false>
 __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (weighted_waves_per_simd<Geo<R_, C_, VAR>>())) void playout_weighted_kernel(const WeightedPlayoutParams SP) {
     using G = Geo<R_, C_, VAR>;
     constexpr int KIND = 8;
@@ -124,7 +127,8 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (weighted_waves_per_s
                                                                                                                           nullptr, &carry, false, &tp->play);
         if (!(carry.flags & F_OVER)) draw(tp, slot_t, lane_t);
     }
-    store_results(top->play.out, env, lane, carry.flags);
+    if constexpr (LEAF) store_results_leaf(LW[slot], top->play.out, top->leaf, env, lane, carry.flags);
+    else store_results(top->play.out, env, lane, carry.flags);
     int32_t *const o_length = top->play.length;
     if (lane == 0 && o_length) o_length[env] = t;
     write_final_record(LW[slot], P, env, carry, lane);

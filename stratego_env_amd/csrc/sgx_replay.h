@@ -18,6 +18,7 @@ struct ReplayArgs {
 struct ReplayParams {
     KParams k;
     ReplayArgs rep;
+    LeafParams leaf;      // read by the LEAF instantiation alone
 };
 
 // One chunk of a game's list: lane j of the game's LPG lanes takes entry t0 + j, one load instruction per chunk (contiguous 4 * LPG bytes
@@ -35,7 +36,7 @@ __device__ __forceinline__ int replay_chunk(const int32_t *lane_entry0, const in
 // both requested before the workgroup stages its tables; a move takes its entry from `cur` with a cross-lane read inside the game's own lanes,
 // and when a chunk is used up `nxt` becomes `cur` and the chunk after it is requested -- LPG moves before its first entry is needed.
 // The loop is bounded by a COUNT, len <= max_len; it advances one entry per pass whether the entry was applied or passed over.
-template <int R_, int C_, int VAR = 0>
+template <int R_, int C_, int VAR = 0, bool LEAF = false>
 __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd<Geo<R_, C_, VAR>, 8>())) void replay_kernel(const ReplayParams SP) {
     using G = Geo<R_, C_, VAR>;
     constexpr int KIND = 8;
@@ -84,7 +85,8 @@ __global__ __launch_bounds__((64 * Geo<R_, C_, VAR>::WPB), (steps_waves_per_simd
             nxt = replay_chunk(lane_entry0, tp->rep.step_stride, (int64_t)c + G::LPG, lane_t, len);
         }
     }
-    store_results(top->rep.out, env, lane, carry.flags);
+    if constexpr (LEAF) store_results_leaf(LW[slot], top->rep.out, top->leaf, env, lane, carry.flags);
+    else store_results(top->rep.out, env, lane, carry.flags);
     uint8_t *const o_stop = top->rep.stop;
     int32_t *const o_applied = top->rep.applied, *const o_consumed = top->rep.consumed;
     if (lane == 0 && o_stop) o_stop[env] = (uint8_t)stop;

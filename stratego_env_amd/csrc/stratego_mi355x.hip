@@ -160,6 +160,10 @@ struct sgx_env {
     int32_t *count_scratch;
     int64_t *scan_sums;
     int64_t count_scratch_cap, scan_sums_cap;
+    // sgx_set_leaf_values: the handle's device copy of the table (int16 [LEAF_ROWS][cells], zeros behind the caller's 28 rows; NULL = none)
+    // and what goes with it into the launches this handle is dst of
+    int16_t *leaf_table;
+    int32_t leaf_limit, leaf_denom, leaf_see_all;
 };
 
 namespace {
@@ -543,6 +547,7 @@ SGX_API int sgx_destroy(sgx_env *h) {
     if (h->ring_tab_ev) (void)hipEventDestroy(h->ring_tab_ev);
     if (h->count_scratch) (void)hipFree(h->count_scratch);
     if (h->scan_sums) (void)hipFree(h->scan_sums);
+    if (h->leaf_table) (void)hipFree(h->leaf_table);
     delete h;
     return SGX_OK;
 }
@@ -678,6 +683,36 @@ SGX_API int sgx_set_start_pool(sgx_env *h, sgx_env *pool, int64_t n_pool, int32_
     h->pool_flags = flags & SGX_POOL_RANDOM_FIRST_PLAYER;
     return SGX_OK;
 }
+
+SGX_API int sgx_set_leaf_values(sgx_env *h, const int16_t *table_host, int32_t limit, int32_t denom, int32_t flags) {
+    if (!h) return fail(SGX_EINVAL, "sgx_set_leaf_values: handle is NULL%s");
+    if (!table_host) {                                       // clear: positions that are not over report 0, 0 again
+        if (!h->leaf_table) return SGX_OK;
+        SGX_ON_DEVICE(h->device);
+        HIP_TRY(hipDeviceSynchronize());                     // (no launch that reads the buffer is in flight when it goes)
+        HIP_TRY(hipFree(h->leaf_table));
+        h->leaf_table = nullptr; h->leaf_limit = h->leaf_denom = h->leaf_see_all = 0;
+        return SGX_OK;
+    }
+    if (denom < 1 || denom > (1 << 24) || limit < 1 || limit > denom)
+        return fail(SGX_EINVAL, "%s", ("sgx_set_leaf_values: 1 <= limit <= denom <= 2^24 is required (got limit = " + std::to_string(limit) + ", denom = " + std::to_string(denom) + ")").c_str());
+    if (flags & ~SGX_LEAF_SEE_ALL) return fail(SGX_EINVAL, "sgx_set_leaf_values: unknown flag bits%s");
+    SGX_ON_DEVICE(h->device);
+    const size_t cells = (size_t)h->cfg.rows * h->cfg.cols;
+    std::vector<int16_t> rows((size_t)LEAF_ROWS * cells, 0);
+    memcpy(rows.data(), table_host, 2 * LEAF_HALF * cells * sizeof(int16_t));
+    int16_t *buf_dev = nullptr;
+    if (hipMalloc((void **)&buf_dev, rows.size() * sizeof(int16_t)) != hipSuccess) { (void)hipGetLastError(); return fail(SGX_ENOMEM, "sgx_set_leaf_values: device allocation failed%s"); }
+    hipError_t e = hipMemcpy(buf_dev, rows.data(), rows.size() * sizeof(int16_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();         // the launches in flight have finished with the old table: it goes only now
+    if (e != hipSuccess) { (void)hipFree(buf_dev); return fail(SGX_EDEVICE, "sgx_set_leaf_values: %s", hipGetErrorString(e)); }
+    if (h->leaf_table) (void)hipFree(h->leaf_table);
+    h->leaf_table = buf_dev;
+    h->leaf_limit = limit; h->leaf_denom = denom; h->leaf_see_all = (flags & SGX_LEAF_SEE_ALL) ? 1 : 0;
+    return SGX_OK;
+}
+
+SGX_API int sgx_leaf_values_set(const sgx_env *h) { return (h && h->leaf_table) ? 1 : 0; }
 
 SGX_API int sgx_set_start_index_out(sgx_env *h, int32_t *start_index_dev) {
     if (!h) return fail(SGX_EINVAL, "sgx_set_start_index_out: handle is NULL%s");
@@ -2178,11 +2213,12 @@ ResultOut result_out(const IO &io) { return ResultOut{io.reward_dev, io.done_dev
 
 // One launch of a pool-to-pool kernel (sgx_pool_frame.h) over sp.k's envs: the geometry of the logic-only launches.  K names the kernel
 // template: K::kernel<R, C, VAR>() is the instantiation.
-struct PlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_kernel<R, C, VAR>; } };
-struct WeightedPlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_weighted_kernel<R, C, VAR>; } };
-struct ReplayK { template <int R, int C, int VAR> static auto kernel() { return &replay_kernel<R, C, VAR>; } };
+// (LEAF: the instantiation that evaluates positions that are not over, launched when dst has leaf values set -- launch_leaf_or_plain)
+template <bool LEAF> struct PlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_kernel<R, C, VAR, LEAF>; } };
+template <bool LEAF> struct WeightedPlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_weighted_kernel<R, C, VAR, LEAF>; } };
+template <bool LEAF> struct ReplayK { template <int R, int C, int VAR> static auto kernel() { return &replay_kernel<R, C, VAR, LEAF>; } };
 struct CountK { template <int R, int C, int VAR> static auto kernel() { return &count_kernel<R, C, VAR>; } };
-struct ChildrenK { template <int R, int C, int VAR> static auto kernel() { return &children_kernel<R, C, VAR>; } };
+template <bool LEAF> struct ChildrenK { template <int R, int C, int VAR> static auto kernel() { return &children_kernel<R, C, VAR, LEAF>; } };
 template <class K, class SP>
 int launch_pool_kernel(const sgx_env *h, SP &sp, void *stream) {
     int32_t w[8];
@@ -2198,6 +2234,15 @@ int launch_pool_kernel(const sgx_env *h, SP &sp, void *stream) {
         })) return rc;
     HIP_TRY(hipGetLastError());
     return SGX_OK;
+}
+
+// A launch of one of the four kernels that end in store_results, for dst: with leaf values set (sgx_set_leaf_values) the table travels in the
+// launch's parameters and the LEAF instantiation runs; without, the parameters' leaf block stays zero and the plain instantiation runs.
+template <template <bool> class K, class SP>
+int launch_leaf_or_plain(const sgx_env *dst, SP &sp, void *stream) {
+    if (!dst->leaf_table) return launch_pool_kernel<K<false>>(dst, sp, stream);
+    sp.leaf = LeafParams{dst->leaf_table, dst->leaf_limit, dst->leaf_denom, dst->leaf_see_all, 0};
+    return launch_pool_kernel<K<true>>(dst, sp, stream);
 }
 
 // handle scratch of at least `elems` elements (hipFree waits for the launches that still read the old one)
@@ -2276,7 +2321,7 @@ SGX_API int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev
     if (int rc = check_aligned("sgx_playout", "length_dev", io->length_dev, 4)) return rc;
     SGX_ON_DEVICE(dst->device);
     PlayoutParams sp{pool_params(dst, src, src_index_dev, 0), PlayParams{draw, result_out(*io), io->length_dev, io->max_steps}};
-    if (int rc = launch_pool_kernel<PlayoutK>(dst, sp, stream)) return rc;
+    if (int rc = launch_leaf_or_plain<PlayoutK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_PLAYOUT;
     return SGX_OK;
 }
@@ -2303,7 +2348,7 @@ SGX_API int sgx_playout_weighted(sgx_env *dst, sgx_env *src, const int32_t *src_
     WeightedPlayoutParams sp{pool_params(dst, src, src_index_dev, 0), PlayParams{draw, result_out(*io), io->length_dev, io->max_steps},
                              (policy_flags & SGX_PLAYOUT_SEE_ALL) ? 1 : 0, 0, {}};
     memcpy(sp.weights, weights, sizeof(sp.weights));       // the table leaves with the launch's arguments: the caller's copy is free again
-    if (int rc = launch_pool_kernel<WeightedPlayoutK>(dst, sp, stream)) return rc;
+    if (int rc = launch_leaf_or_plain<WeightedPlayoutK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_PLAYOUT_WEIGHTED;
     return SGX_OK;
 }
@@ -2335,7 +2380,7 @@ SGX_API int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
                                (io->flags & SGX_REPLAY_SKIP_INVALID) ? 1 : 0}};
     // the step's decode flags the replay's flags translate to
     sp.k.io.flags = ((io->flags & SGX_REPLAY_ACTIONS_1D) ? SGX_STEP_ACTIONS_1D : 0) | ((io->flags & SGX_REPLAY_ALLOW_OSCILLATION) ? SGX_STEP_ALLOW_OSCILLATION : 0);
-    if (int rc = launch_pool_kernel<ReplayK>(dst, sp, stream)) return rc;
+    if (int rc = launch_leaf_or_plain<ReplayK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_REPLAY;
     return SGX_OK;
 }
@@ -2389,7 +2434,7 @@ SGX_API int sgx_expand_all(sgx_env *dst, sgx_env *src, const int32_t *src_index_
     ChildrenParams sp{pool_params(dst, src, src_index_dev, 0),
                       ChildrenArgs{io->offsets_dev, io->parent_dev, io->action_dev, result_out(*io), io->n_roots, io->first_child, (io->flags & SGX_CHILDREN_ACTIONS_1D) ? 1 : 0}};
     sp.k.n_envs = io->n_children;
-    return launch_pool_kernel<ChildrenK>(dst, sp, stream);
+    return launch_leaf_or_plain<ChildrenK>(dst, sp, stream);
 }
 
 SGX_API int sgx_state_keys(sgx_env *src, const int32_t *src_index_dev, int64_t n, int32_t view, int32_t flags, uint64_t *keys_dev, void *stream) {

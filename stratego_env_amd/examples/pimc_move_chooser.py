@@ -1,11 +1,13 @@
 """Perfect-information Monte Carlo move choice for B live games at once, on the device: the loop playouts were built for.
 
     python -m stratego_env_amd.examples.pimc_move_chooser [--version fives] [--games 8] [--worlds 4] [--steps 6] [--biased] [--setup-prior]
+                                                          [--max-steps 16 --leaf]
 
 For every game the mover does not see the opponent's piece types.  PIMC samples W worlds that look the same to the mover
 (PackedStates.determinize), tries every valid root action in every world (PackedStates.expand, whose parent_index fans the worlds out over
 the actions), plays each child to the end with random moves (PackedStates.playout) and picks the action with the best mean result from the
-mover's side.  Three library calls and plain torch around them; nothing leaves the device until the chosen actions do, and the live env
+mover's side -- or, with max_steps and a leaf-value table, only max_steps moves deep, the position reached scored by the table
+(PackedStates.set_leaf_values): without the table a playout that is cut off reports 0, 0 and says nothing.  Three library calls and plain torch around them; nothing leaves the device until the chosen actions do, and the live env
 is only read.
 """
 import argparse
@@ -16,14 +18,17 @@ from stratego_env_amd.procedural_env import PackedStates
 from stratego_env_amd.vec_env import VecStrategoEnv
 
 
-def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see_all=True, beliefs=None):
+def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see_all=True, beliefs=None, leaf=None):
     """env: a live VecStrategoEnv of B games.  -> (actions int64 [B]: the chosen absolute 1-D action per game, -1 where the game is over;
     values float32 [B, action_size]: the mean playout result of every valid root action from the root mover's side, -inf elsewhere).
     The worlds and the playouts are keyed by (seed, slot, draw): the same arguments give the same choice.
     weights: None = uniformly random playouts; else a [4, 13, 14] weight table (stratego_env_amd.playout_policies) the playouts draw their
     moves by; see_all (with weights only): the playout players look at the sampled world's true piece types, as PIMC assumes.
     beliefs: None = worlds sampled uniformly; else a [2, 12, cells] belief table (stratego_env_amd.beliefs; numpy or a device tensor) the
-    hidden pieces are dealt by (PackedStates.determinize(..., beliefs=...))."""
+    hidden pieces are dealt by (PackedStates.determinize(..., beliefs=...)).
+    leaf: None = a playout cut off by max_steps counts 0; else (table, limit, denom) as PackedStates.set_leaf_values takes them
+    (stratego_env_amd.leaf_values builds tables): the position a cut-off playout reached is scored by the table, on the sampled world's
+    true pieces."""
     B, W, dev = env.num_envs, int(n_worlds), env.device
     dev_index = dev.index
     info = env.env_info()
@@ -50,6 +55,9 @@ def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see
             children = PackedStates(env.variant, W * M, device=dev_index, seed=seed)
             valid, _ = children.expand(worlds, action.repeat(W).to(torch.int32), parent_index=parent)
             assert bool(valid.all())
+            if leaf is not None:
+                table, limit, denom = leaf
+                children.set_leaf_values(table, limit, denom, see_all=True)
             res = children.playout(children, max_steps=max_steps, draw=draw, weights=weights,
                                    see_all=see_all and weights is not None)          # in place: the children are scratch
             value = res.value_for(mover[game].repeat(W))
@@ -71,6 +79,8 @@ def main():
     ap.add_argument('--worlds', type=int, default=4)
     ap.add_argument('--steps', type=int, default=6, help='random moves played before the choice')
     ap.add_argument('--biased', action='store_true', help='playouts that prefer winning attacks and forward moves (playout_policies.capture_biased)')
+    ap.add_argument('--max-steps', type=int, default=0, help='moves per playout (0 = to the end of the game)')
+    ap.add_argument('--leaf', action='store_true', help='score cut-off playouts by material and advance (leaf_values.material / with_advance)')
     ap.add_argument('--setup-prior', action='store_true',
                     help="worlds dealt by where humans place their pieces (beliefs.setup_prior; --version barrage or standard)")
     args = ap.parse_args()
@@ -85,7 +95,12 @@ def main():
     if args.setup_prior:
         from stratego_env_amd.beliefs import setup_prior
         beliefs = setup_prior(args.version)
-    actions, values = choose_moves(env, args.worlds, weights=weights, beliefs=beliefs)
+    leaf = None
+    if args.leaf:
+        from stratego_env_amd import leaf_values
+        denom = 2 * leaf_values.side_total(args.version)
+        leaf = (leaf_values.with_advance(leaf_values.material(args.version), 1, rows=env.variant.rows), denom - 1, denom)
+    actions, values = choose_moves(env, args.worlds, max_steps=args.max_steps, weights=weights, beliefs=beliefs, leaf=leaf)
     for b, a in enumerate(actions.tolist()):
         if a < 0:
             print("game %d: over" % b)

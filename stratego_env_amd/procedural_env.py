@@ -57,6 +57,32 @@ def playout_weights(weights):
     return np.ascontiguousarray(w, dtype=np.uint16)
 
 
+def leaf_table(table, cells):
+    """A leaf-value table as the library takes it: contiguous int16 [2, 14, cells] on the host.  `table`: an array-like of any integer
+    dtype (numpy, or a CPU tensor) of that shape with every entry within int16; ValueError for anything else."""
+    if isinstance(table, torch.Tensor):
+        if table.is_cuda:
+            raise ValueError("the leaf-value table is read on the host: pass a numpy array or a CPU tensor")
+        table = table.numpy()
+    t = np.asarray(table)
+    if t.dtype.kind not in 'iu':
+        raise ValueError("the leaf-value table must have an integer dtype (got %s): round it yourself (leaf_values documents how it rounds)" % t.dtype)
+    if t.shape != (2, 14, cells):
+        raise ValueError("the leaf-value table must have shape [2, 14, %d] = [mine / theirs][piece][cell] (got %s)" % (cells, tuple(t.shape)))
+    if t.size and (int(t.min()) < -32768 or int(t.max()) > 32767):
+        bad = np.argwhere((t < -32768) | (t > 32767))[0]
+        raise ValueError("table[%d][%d][%d] = %d is outside int16" % (bad[0], bad[1], bad[2], int(t[tuple(bad)])))
+    return np.ascontiguousarray(t, dtype=np.int16)
+
+
+def leaf_scale(limit, denom):
+    """(limit, denom) of a leaf-value setting as ints; ValueError unless 1 <= limit <= denom <= 2^24."""
+    limit, denom = int(limit), int(denom)
+    if not 1 <= limit <= denom <= _lib.LEAF_MAX_DENOM:
+        raise ValueError("1 <= limit <= denom <= 2^24 is required (got limit = %d, denom = %d)" % (limit, denom))
+    return limit, denom
+
+
 class BatchedStrategoProceduralEnv:
     def __init__(self, version, batch_size, device=0):
         self.variant = get_variant(version)
@@ -521,13 +547,24 @@ class BatchedStrategoProceduralEnv:
         finally:
             src.close()
 
+    def evaluate(self, states, players, table, limit, denom, see_all=False):
+        """The leaf values of every state by a piece-square table (PackedStates.set_leaf_values / evaluate: pack -> evaluate in place, for
+        callers on the reference layout): float32 [n, 2] on the device = (v(+1), v(-1)) of a state that is not over, the final rewards of
+        a finished one.  table / limit / denom / see_all: as PackedStates.set_leaf_values takes them.  No reference counterpart."""
+        src = self.pack(states, players)
+        try:
+            return src.set_leaf_values(table, limit, denom, see_all=see_all).evaluate()
+        finally:
+            src.close()
+
     def close(self):
         self._vec.close()
 
 
 class PlayoutResult:
     """What PackedStates.playout reports per slot (device tensors): reward float32 [n,2] = the final position's rewards of players +1 / -1
-    (+-1 for a win, the reference's tie value, 0, 0 for a max-turn ending and for a playout cut off by max_steps), done uint8 (0 = cut off),
+    (+-1 for a win, the reference's tie value, 0, 0 for a max-turn ending and for a playout cut off by max_steps -- with
+    set_leaf_values on the pool a cut-off playout reports the leaf values of the position it reached instead), done uint8 (0 = cut off),
     ending_invalid uint8 (the max-turn tie), player int8 (the mover at the final position), length int32 (moves played)."""
 
     def __init__(self, reward, done, ending_invalid, player, length):
@@ -789,6 +826,42 @@ class PackedStates:
             _lib.check(vec._L.sgx_expand_all(vec._h, src_vec._h, None if si is None or n_roots == 0 else si.data_ptr(), io, vec._stream()), vec._L)
         vec._next_actions_fresh = False
         return res
+
+    def set_leaf_values(self, table, limit, denom, see_all=False):
+        """Leaf values for the calls this pool is the DESTINATION of (sgx_set_leaf_values; the rule is in include/stratego_mi355x.h):
+        playout, replay and expand_all then report, for every slot whose position is not over, reward = (v(+1), v(-1)) instead of 0, 0,
+        with v(p) = clamp(mine(p) - theirs(p), -limit, limit) / denom.  table: an integer array-like [2, 14, cells] within int16
+        (stratego_env_amd.leaf_values builds them): table[0][t][cell] is the worth of an own piece of type t (1..12) on `cell` of its
+        owner's perspective, table[1][d][cell] the worth of an opponent's piece shown as d (1..12 revealed, 13 unknown; see_all=True:
+        its true type) on `cell` of that opponent's perspective.  1 <= limit <= denom <= 2^24.  Shape and range are checked on the host;
+        the call waits for the device once (launches in flight keep the table they started with).  The table is a setting of this pool,
+        not part of its records: copies and snapshots do not carry it."""
+        vec = self._vec
+        t = leaf_table(table, vec.variant.rows * vec.variant.columns)
+        limit, denom = leaf_scale(limit, denom)
+        with torch.cuda.device(self.device):
+            _lib.check(vec._L.sgx_set_leaf_values(vec._h, t.ctypes.data_as(C.c_void_p), limit, denom, _lib.LEAF_SEE_ALL if see_all else 0), vec._L)
+        return self
+
+    def clear_leaf_values(self):
+        """Positions that are not over report 0, 0 again (waits for the device if a table was set)."""
+        vec = self._vec
+        with torch.cuda.device(self.device):
+            _lib.check(vec._L.sgx_set_leaf_values(vec._h, None, 0, 0, 0), vec._L)
+        return self
+
+    @property
+    def leaf_values_set(self):
+        return bool(self._vec._L.sgx_leaf_values_set(self._vec._h))
+
+    def evaluate(self, src=None, src_index=None):
+        """The leaf values of src[src_index[i]] (None: of this pool's own records, in place) by this pool's table: float32 [n, 2] on the
+        device, (v(+1), v(-1)) for a position that is not over and the final rewards for a finished one.  It is the replay of an empty
+        list (max_len = 0): with another pool as `src` the records are copied here on the way.  Raises if no table is set."""
+        if not self.leaf_values_set:
+            raise ValueError("evaluate needs leaf values: call set_leaf_values first")
+        empty = torch.empty((self.n, 0), dtype=torch.int32, device=self.device)
+        return self._vec.replay(self if src is None else src, empty, src_index=src_index).reward
 
     @property
     def last_launch_kind(self):

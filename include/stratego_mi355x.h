@@ -149,6 +149,8 @@ typedef struct sgx_step_io {
  *   sgx_playout_weighted         as sgx_playout; `weights` is HOST memory, read before the call returns (any uint16_t alignment): the
  *                                contract has nothing to add for it
  *   sgx_replay                   src_index_dev, actions_dev, lengths_dev, applied_dev, consumed_dev, reward_dev 4; stop_dev, done_dev, ending_invalid_dev, player_dev 1
+ *   sgx_set_replay_origins       origin_in_dev, origin_out_dev 4 (their elements are read and written as 2-byte values; an odd board's rows
+ *                                start at any 2-byte phase from there)
  *   sgx_count_moves              src_index_dev, counts_dev 4; offsets_dev 16
  *   sgx_expand_all               src_index_dev, parent_dev, action_dev, reward_dev 4; offsets_dev 16; done_dev, ending_invalid_dev, player_dev 1
  *   sgx_state_keys               src_index_dev 4; keys_dev 8 (16 with SGX_KEYS_WIDE: one 16-byte store per record)
@@ -300,6 +302,7 @@ int sgx_set_steps_barrier(sgx_env *h, int32_t mode);
 #define SGX_LAUNCH_REPLAY 5      /* sgx_replay: one wave per game, every entry of the action list in one launch (set on dst) */
 #define SGX_LAUNCH_CHILDREN 6    /* sgx_expand_all: one wave per child, root found from the offsets, mask regenerated, move applied (set on dst) */
 #define SGX_LAUNCH_PLAYOUT_WEIGHTED 7   /* sgx_playout_weighted: sgx_playout's launch with the weighted draw (set on dst) */
+#define SGX_LAUNCH_REPLAY_TRACKED 8      /* sgx_replay while dst has sgx_set_replay_origins set: sgx_replay's launch, with the piece labels (set on dst) */
 int sgx_last_launch_kind(const sgx_env *h);
 
 /* Shares of the eight XCDs in a launch of sgx_step / sgx_observe.  Under a saturating write stream the odd XCDs of MI355X drain their
@@ -602,14 +605,14 @@ int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const s
  * `draw` gives independent ones, and no draw of a rollout moves.  hidden_dev: int32 [dst's N] (NULL = not wanted) = number of hidden cells that
  * were shuffled; -1 marks a record with a flag or a bomb on a moved hidden cell, which play cannot produce: it is copied unchanged.
  * A sampled world agrees with everything the record tracks (what the reference's state tracks), NOT with the full move history: a piece that
- * has acted in ways only some types can may still be dealt another type.  src == dst with a NULL index works in place; with an index it
+ * has acted in ways only some types can may still be dealt another type (sgx_determinize_weighted takes such knowledge as weights).  src == dst with a NULL index works in place; with an index it
  * would race and is SGX_EINVAL, like an observer outside {-1, 0, 1}, a handle of another variant or a misaligned pointer (4 bytes).
  * No reference counterpart. */
 int sgx_determinize(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, int32_t observer, uint64_t draw, int32_t *hidden_dev, void *stream);
 
 /* Determinization from a belief: sgx_determinize with caller-given weights of (opponent type, cell) in the place of the uniform deal -- a
- * tracker over the move history, a network or a prior over setups (stratego_env_amd/beliefs.py) says where the opponent's pieces are likely
- * to stand, and the worlds are drawn accordingly, in the same single launch, pool to pool, with the same key and the same guarantees.
+ * network or a prior over setups (stratego_env_amd/beliefs.py; carried along the moves of each game by the labels of a tracked replay,
+ * sgx_set_replay_origins, and beliefs.follow) says where the opponent's pieces are likely to stand, and the worlds are drawn accordingly, in the same single launch, pool to pool, with the same key and the same guarantees.
  * THE RULE (tests/determinize_weighted_rule.py restates it in numpy, bit for bit).  For slot i of dst:
  *   s = src_index[i] (i when the index is NULL), g = dst's env_id_offset + i.
  *   opp, H, A, B are exactly those of sgx_determinize: opp = the observer's opponent, H = opp's cells whose public layer says 13, A = the
@@ -768,6 +771,41 @@ typedef struct sgx_replay_io {
     int32_t max_len, flags;
 } sgx_replay_io;                  /* 9 pointers + 3 int64 + 2 int32 = 104 bytes */
 int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_replay_io *io, void *stream);
+
+/* Piece origins: a replay that also says, for every piece on the board at its end, WHICH piece it is -- by default the cell it stood on at
+ * the replay's root.  The record cannot say that (it carries types, what the opponent has seen, and which cells never moved, not identity),
+ * and a setup prior is a statement about setup cells: with the origins of a replay from the setup, "what stands on cell c now" becomes "what
+ * was deployed on cell origin[c]" (stratego_env_amd.beliefs.follow), which is what sgx_determinize_weighted's per-record tables want.
+ * A SETTING OF THE dst HANDLE, like sgx_set_start_index_out: while origin_out_dev is set, every sgx_replay whose dst is h also tracks the
+ * labels, on the call's stream like the rest of its work, and sets dst's sgx_last_launch_kind to SGX_LAUNCH_REPLAY_TRACKED.  The setter
+ * stores the two caller-owned device pointers, launches nothing and waits for nothing; the caller keeps the tensors alive while the setting
+ * holds.  Every byte sgx_replay writes without the setting -- the records and the seven result tensors, with or without leaf values on dst --
+ * it writes the same with it; without the setting nothing changes anywhere.
+ *   origin_out_dev  int16 [dst N][2][cells]       written whole for every slot
+ *   origin_in_dev   int16 [src envs][2][cells]    nullable; read at record s = src_index[i] (i without an index), as belief_dev is addressed
+ *   Player index 0 is player +1 and 1 is player -1, as the state's layers; cells are absolute, cell = r * C + c.
+ * THE RULE is defined on the reference states the replay passes through, not on the record (tests/origins_rule.py restates it in numpy on
+ * the CPU oracle).  own(q) = state layer q (true pieces).
+ *   Start: Lab[q][c] = (origin_in[s][q][c] if origin_in_dev is given, else c) where own(q)(root)[c] != 0, and -1 everywhere else.  A given
+ *   label is an opaque int16 carried verbatim (origins are the default, any piece id works); what origin_in holds on empty cells is ignored.
+ *   Every applied entry (step 4 of the replay's rule) taking pos to pos', mover index q, opponent q':
+ *     a = the one cell with own(q)(pos)[a] != 0 and own(q)(pos')[a] == 0;
+ *     Lab'[q] = Lab[q], except Lab'[q][a] = -1, and, if some cell b has own(q)(pos)[b] == 0 and own(q)(pos')[b] != 0 (the mover stands there
+ *     after a move to an empty cell or a won attack), Lab'[q][b] = Lab[q][a];
+ *     Lab'[q'][c] = Lab[q'][c] where own(q')(pos')[c] != 0, else -1.
+ *   So a lost or drawn attack drops the mover's label, a won or drawn attack the defender's; a flag capture is a won attack.  (A valid no-op
+ *   entry -- the mover has no move -- moves no piece: no cell a, nothing changes.)  Entries passed over (SGX_REPLAY_SKIP_INVALID) or refused
+ *   change nothing.
+ *   Output: Lab at the final position, whole, for every slot; a copy-only call (max_len == 0) writes the start labels.
+ * Aliasing, checked by sgx_replay before anything is launched: with a NULL src_index_dev origin_in_dev == origin_out_dev is legal (a game's
+ * labels are read whole before they are written, as its record is); any other overlap of the ranges src envs * 2 * cells and N * 2 * cells
+ * elements, and with an index any overlap at all, is SGX_EINVAL.  Also SGX_EINVAL, from the setter: a NULL handle, a pointer that is not
+ * 4-byte aligned.  A NULL origin_out_dev clears the setting (origin_in_dev is then ignored).
+ * The setting is not game state: sgx_copy_envs, snapshots and start pools do not carry it, and sgx_destroy frees nothing for it.  Live
+ * stepping, playouts and sgx_expand_all do not track.  Added without a change to an existing struct or signature: SGX_ABI_VERSION stays.
+ * Reference counterpart: none -- a dict of piece ids kept by the caller next to env.step() in a loop. */
+int sgx_set_replay_origins(sgx_env *h, const int16_t *origin_in_dev /* nullable */, int16_t *origin_out_dev /* NULL = clear */);
+int sgx_replay_origins_set(const sgx_env *h);   /* 1 / 0 */
 
 /* Expand all: every valid move of every root, pool to pool -- "all children of these nodes", what MCTS / ISMCTS node expansion, an
  * exhaustive shallow search and a perft-style check of the move generator start with -- without a mask, a nonzero() or an action list on

@@ -21,6 +21,7 @@ STEP_COMPACT_OBS, STEP_COMPACT_MASK = 128, 256
 OUT_FULL_OBS, OUT_MAX_TRIALS = 1024, 64
 POOL_RANDOM_FIRST_PLAYER, POOL_RESTART_CLOCK = 1, 2
 LAUNCH_WAVE, LAUNCH_LANE, LAUNCH_MULTI_STEP, LAUNCH_MULTI_STEP_WAVE, LAUNCH_PLAYOUT, LAUNCH_REPLAY, LAUNCH_CHILDREN = 0, 1, 2, 3, 4, 5, 6
+LAUNCH_REPLAY_TRACKED = 8
 LAUNCH_PLAYOUT_WEIGHTED = 7
 PLAYOUT_SEE_ALL = 1
 PLAYOUT_WEIGHTS_SHAPE, PLAYOUT_WEIGHT_MAX = (4, 13, 14), 4095
@@ -36,7 +37,7 @@ EXPORTED_SYMBOLS = (
     'sgx_abi_version', 'sgx_build_id', 'sgx_supports_geometry', 'sgx_last_error', 'sgx_num_envs', 'sgx_record_bytes', 'sgx_spatial_channels', 'sgx_num_spatial_actions',
     'sgx_action_size_1d', 'sgx_build_obs_lut', 'sgx_build_full_obs_lut', 'sgx_build_original_obs_lut', 'sgx_create', 'sgx_destroy', 'sgx_set_nt_stores', 'sgx_set_lane_kernel', 'sgx_set_half_wave', 'sgx_set_steps_barrier', 'sgx_set_multi_step', 'sgx_last_launch_kind', 'sgx_set_xcd_skew', 'sgx_set_xcd_shares', 'sgx_get_xcd_shares', 'sgx_set_setup_table', 'sgx_set_start_pool', 'sgx_set_start_index_out', 'sgx_start_pool_size', 'sgx_reset',
     'sgx_observe', 'sgx_time_observe', 'sgx_mem_probe', 'sgx_store_probe', 'sgx_alloc_outputs', 'sgx_set_placement_target', 'sgx_free_outputs', 'sgx_step', 'sgx_host_alloc', 'sgx_host_free', 'sgx_step_sync', 'sgx_step_n', 'sgx_step_ring', 'sgx_step_traj', 'sgx_rollout', 'sgx_compact_obs_stride', 'sgx_compact_mask_words', 'sgx_decode_obs', 'sgx_decode_mask', 'sgx_sample_valid', 'sgx_choose_actions', 'sgx_export_state', 'sgx_import_state', 'sgx_import_state_checked', 'sgx_step_states', 'sgx_set_general_states', 'sgx_copy_envs', 'sgx_expand', 'sgx_determinize', 'sgx_determinize_weighted', 'sgx_playout', 'sgx_playout_weighted', 'sgx_replay', 'sgx_count_moves', 'sgx_expand_all', 'sgx_state_keys', 'sgx_get_env_info',
-    'sgx_set_leaf_values', 'sgx_leaf_values_set',
+    'sgx_set_leaf_values', 'sgx_leaf_values_set', 'sgx_set_replay_origins', 'sgx_replay_origins_set',
 )
 
 
@@ -146,6 +147,10 @@ def _bind(L):
     L.sgx_set_leaf_values.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32]
     L.sgx_leaf_values_set.restype = C.c_int
     L.sgx_leaf_values_set.argtypes = [vp]
+    L.sgx_set_replay_origins.restype = C.c_int
+    L.sgx_set_replay_origins.argtypes = [vp, vp, vp]
+    L.sgx_replay_origins_set.restype = C.c_int
+    L.sgx_replay_origins_set.argtypes = [vp]
     L.sgx_set_start_index_out.restype = C.c_int
     L.sgx_set_start_index_out.argtypes = [vp, vp]
     L.sgx_start_pool_size.restype = i64

@@ -1,5 +1,5 @@
 """Belief tables for weighted determinization (PackedStates.determinize(..., beliefs=...), sgx_determinize_weighted).  Host only, plain
-numpy; move a table to the device with torch.from_numpy(table.astype(numpy.int32)).cuda().
+numpy; move a table to the device with torch.from_numpy(table.astype(numpy.int32)).cuda().  (`follow` alone also takes device tensors.)
 
 A table is uint16 [2, 12, cells], read as beliefs[player index of the piece's owner][type - 1][absolute cell], every entry in [0, 4095]:
   player     0 = player +1, 1 = player -1 (as the layers of a state are); a determinization reads the block of the observer's OPPONENT;
@@ -87,7 +87,7 @@ def setup_prior(name):
     that has moved can stand: a movable type (1..10) gets, on each of those cells, its mean weight over the setup-row cells, rounded half
     up and at least 1; flag and bomb get 0 there.
     A heuristic prior on where humans place pieces -- not a posterior: it knows nothing of the moves played, and the weights of a moved
-    piece's cells say only how common the type is."""
+    piece's cells say only how common the type is.  `follow` turns it into a table per game that does know where each piece started."""
     v = get_variant(name)
     R, C, U = v.rows, v.columns, v.initial_state_usable_rows
     counts = setup_counts(name)
@@ -109,3 +109,52 @@ def setup_prior(name):
                 w[t - 1, ~inside] = max(1, (2 * total + n_in) // (2 * n_in))
         out[p] = w
     return out.astype(np.uint16)
+
+
+def follow(prior, origins):
+    """A prior over SETUP cells carried along the moves of every game: out[i][p][t][c] = prior[(i,) p][t][origins[i][p][c]] where the
+    label lies in [0, cells), else 0.  origins: int16 [n, 2, cells], the labels of a tracked replay from the games' start positions
+    (replay(..., track_origins=True).origins; sgx_set_replay_origins): origins[i][p][c] is the cell the piece of player index p on cell c of
+    game i stood on at the start, -1 where it has none.  prior: [2, 12, cells] (one for all games) or [n, 2, 12, cells].
+    -> [n, 2, 12, cells] of prior's dtype, one table per record as determinize(..., beliefs=...) takes it: the weight of type t on a cell
+    is what the prior said of type t on the cell its piece was DEPLOYED on, so a piece that walked off its setup rows keeps the weights
+    of where it came from, and a one-hot prior on the true setup stays one-hot on the truth.  Cells without a piece get weight 0 for every
+    type; a determinization never reads them.
+    numpy in -> numpy out; torch tensors in (both on one device) -> a tensor there, nothing synchronised.  The device form gathers each
+    player's transposed [cells, 12] block (per game: [n, cells, 12]) with the [n, cells] labels, so no index as large as the result is built."""
+    if isinstance(prior, np.ndarray) and isinstance(origins, np.ndarray):
+        o = origins.astype(np.int64)
+        if o.ndim != 3 or o.shape[1] != 2:
+            raise ValueError("origins must have shape [n, 2, cells] (got %s)" % (tuple(origins.shape),))
+        n, _, cells = o.shape
+        if tuple(prior.shape) not in ((2, TYPES, cells), (n, 2, TYPES, cells)):
+            raise ValueError("prior must have shape [2, 12, %d] or [%d, 2, 12, %d] (got %s)" % (cells, n, cells, tuple(prior.shape)))
+        ok = (o >= 0) & (o < cells)
+        idx = np.where(ok, o, 0)
+        out = np.empty((n, 2, TYPES, cells), dtype=prior.dtype)
+        for p in range(2):
+            if prior.ndim == 3:
+                out[:, p] = prior[p].T[idx[:, p]].transpose(0, 2, 1)                         # [cells, 12] rows by label
+            else:
+                out[:, p] = np.take_along_axis(prior[:, p], idx[:, p, None, :], axis=2)
+        return out * ok[:, :, None, :].astype(prior.dtype)
+    import torch
+    if not isinstance(prior, torch.Tensor) or not isinstance(origins, torch.Tensor):
+        raise ValueError("follow takes numpy arrays, or torch tensors on one device")
+    if origins.dim() != 3 or origins.shape[1] != 2:
+        raise ValueError("origins must have shape [n, 2, cells] (got %s)" % (tuple(origins.shape),))
+    n, _, cells = (int(x) for x in origins.shape)
+    if tuple(prior.shape) not in ((2, TYPES, cells), (n, 2, TYPES, cells)) or prior.device != origins.device:
+        raise ValueError("prior must have shape [2, 12, %d] or [%d, 2, 12, %d] on the labels' device (got %s on %s)"
+                         % (cells, n, cells, tuple(prior.shape), prior.device))
+    o = origins.to(torch.int64)
+    ok = (o >= 0) & (o < cells)
+    idx = torch.where(ok, o, torch.zeros_like(o))
+    out = torch.empty((n, 2, TYPES, cells), dtype=prior.dtype, device=prior.device)
+    for p in range(2):
+        if prior.dim() == 3:
+            rows = prior[p].t().contiguous()[idx[:, p]]                                      # [n, cells, 12]
+        else:
+            rows = torch.gather(prior[:, p].transpose(1, 2), 1, idx[:, p, :, None].expand(n, cells, TYPES))
+        out[:, p] = (rows * ok[:, p, :, None].to(prior.dtype)).transpose(1, 2)
+    return out

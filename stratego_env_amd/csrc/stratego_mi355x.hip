@@ -164,6 +164,9 @@ struct sgx_env {
     // and what goes with it into the launches this handle is dst of
     int16_t *leaf_table;
     int32_t leaf_limit, leaf_denom, leaf_see_all;
+    // sgx_set_replay_origins: the caller's label tensors (origin_out NULL = none); while set, sgx_replay with this handle as dst tracks labels
+    const int16_t *origin_in;
+    int16_t *origin_out;
 };
 
 namespace {
@@ -713,6 +716,20 @@ SGX_API int sgx_set_leaf_values(sgx_env *h, const int16_t *table_host, int32_t l
 }
 
 SGX_API int sgx_leaf_values_set(const sgx_env *h) { return (h && h->leaf_table) ? 1 : 0; }
+
+SGX_API int sgx_set_replay_origins(sgx_env *h, const int16_t *origin_in_dev, int16_t *origin_out_dev) {
+    // the pointers first: what can be said about them needs no handle
+    if (int rc = check_aligned("sgx_set_replay_origins", "origin_out_dev", origin_out_dev, 4)) return rc;
+    if (origin_out_dev)
+        if (int rc = check_aligned("sgx_set_replay_origins", "origin_in_dev", origin_in_dev, 4)) return rc;
+    if (!h) return fail(SGX_EINVAL, "sgx_set_replay_origins: handle is NULL%s");
+    if (!origin_out_dev) { h->origin_in = nullptr; h->origin_out = nullptr; return SGX_OK; }      // clear (origin_in_dev is ignored)
+    h->origin_in = origin_in_dev;
+    h->origin_out = origin_out_dev;
+    return SGX_OK;
+}
+
+SGX_API int sgx_replay_origins_set(const sgx_env *h) { return (h && h->origin_out) ? 1 : 0; }
 
 SGX_API int sgx_set_start_index_out(sgx_env *h, int32_t *start_index_dev) {
     if (!h) return fail(SGX_EINVAL, "sgx_set_start_index_out: handle is NULL%s");
@@ -2217,6 +2234,7 @@ ResultOut result_out(const IO &io) { return ResultOut{io.reward_dev, io.done_dev
 template <bool LEAF> struct PlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_kernel<R, C, VAR, LEAF>; } };
 template <bool LEAF> struct WeightedPlayoutK { template <int R, int C, int VAR> static auto kernel() { return &playout_weighted_kernel<R, C, VAR, LEAF>; } };
 template <bool LEAF> struct ReplayK { template <int R, int C, int VAR> static auto kernel() { return &replay_kernel<R, C, VAR, LEAF>; } };
+template <bool LEAF> struct ReplayTrackedK { template <int R, int C, int VAR> static auto kernel() { return &replay_kernel<R, C, VAR, LEAF, true>; } };
 struct CountK { template <int R, int C, int VAR> static auto kernel() { return &count_kernel<R, C, VAR>; } };
 template <bool LEAF> struct ChildrenK { template <int R, int C, int VAR> static auto kernel() { return &children_kernel<R, C, VAR, LEAF>; } };
 template <class K, class SP>
@@ -2374,12 +2392,30 @@ SGX_API int sgx_replay(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev,
     if (int rc = check_aligned("sgx_replay", "applied_dev", io->applied_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_replay", "consumed_dev", io->consumed_dev, 4)) return rc;
     if (int rc = check_aligned("sgx_replay", "reward_dev", io->reward_dev, 4)) return rc;
+    if (dst->origin_out && dst->origin_in) {
+        // piece origins (sgx_set_replay_origins): a game's labels are read whole before they are written, as its record is -- so the one
+        // legal overlap of the two tensors is slot i reading what slot i writes
+        const int64_t per = 2 * (int64_t)dst->cfg.rows * dst->cfg.cols;
+        const int16_t *in0 = dst->origin_in, *in1 = in0 + src->n_envs * per, *out0 = dst->origin_out, *out1 = out0 + dst->n_envs * per;
+        const bool overlap = (uintptr_t)in0 < (uintptr_t)out1 && (uintptr_t)out0 < (uintptr_t)in1;
+        if (overlap && src_index_dev) return fail(SGX_EINVAL, "sgx_replay: origin_in_dev overlaps origin_out_dev with an index array (a slot would read labels another has written)%s");
+        if (overlap && in0 != out0) return fail(SGX_EINVAL, "sgx_replay: origin_in_dev and origin_out_dev overlap without being equal%s");
+    }
     SGX_ON_DEVICE(dst->device);
-    ReplayParams sp{pool_params(dst, src, src_index_dev, 0),
-                    ReplayArgs{io->actions_dev, io->lengths_dev, io->applied_dev, io->consumed_dev, io->stop_dev, result_out(*io), io->game_stride, io->step_stride, io->max_len,
-                               (io->flags & SGX_REPLAY_SKIP_INVALID) ? 1 : 0}};
+    const KParams kp = pool_params(dst, src, src_index_dev, 0);
+    const ReplayArgs ra{io->actions_dev, io->lengths_dev, io->applied_dev, io->consumed_dev, io->stop_dev, result_out(*io), io->game_stride, io->step_stride, io->max_len,
+                        (io->flags & SGX_REPLAY_SKIP_INVALID) ? 1 : 0};
     // the step's decode flags the replay's flags translate to
-    sp.k.io.flags = ((io->flags & SGX_REPLAY_ACTIONS_1D) ? SGX_STEP_ACTIONS_1D : 0) | ((io->flags & SGX_REPLAY_ALLOW_OSCILLATION) ? SGX_STEP_ALLOW_OSCILLATION : 0);
+    const int step_flags = ((io->flags & SGX_REPLAY_ACTIONS_1D) ? SGX_STEP_ACTIONS_1D : 0) | ((io->flags & SGX_REPLAY_ALLOW_OSCILLATION) ? SGX_STEP_ALLOW_OSCILLATION : 0);
+    if (dst->origin_out) {                                    // the TRACK instantiations: the same game, and the labels
+        ReplayTrackedParams sp{kp, ra, LeafParams{}, OriginArgs{dst->origin_in, dst->origin_out}};
+        sp.k.io.flags = step_flags;
+        if (int rc = launch_leaf_or_plain<ReplayTrackedK>(dst, sp, stream)) return rc;
+        dst->last_kind = SGX_LAUNCH_REPLAY_TRACKED;
+        return SGX_OK;
+    }
+    ReplayParams sp{kp, ra};
+    sp.k.io.flags = step_flags;
     if (int rc = launch_leaf_or_plain<ReplayK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_REPLAY;
     return SGX_OK;

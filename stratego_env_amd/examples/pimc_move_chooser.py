@@ -18,7 +18,7 @@ from stratego_env_amd.procedural_env import PackedStates
 from stratego_env_amd.vec_env import VecStrategoEnv
 
 
-def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see_all=True, beliefs=None, leaf=None):
+def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see_all=True, beliefs=None, leaf=None, origins=None):
     """env: a live VecStrategoEnv of B games.  -> (actions int64 [B]: the chosen absolute 1-D action per game, -1 where the game is over;
     values float32 [B, action_size]: the mean playout result of every valid root action from the root mover's side, -inf elsewhere).
     The worlds and the playouts are keyed by (seed, slot, draw): the same arguments give the same choice.
@@ -26,6 +26,9 @@ def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see
     moves by; see_all (with weights only): the playout players look at the sampled world's true piece types, as PIMC assumes.
     beliefs: None = worlds sampled uniformly; else a [2, 12, cells] belief table (stratego_env_amd.beliefs; numpy or a device tensor) the
     hidden pieces are dealt by (PackedStates.determinize(..., beliefs=...)).
+    origins (with beliefs): int16 device tensor [B, 2, cells], the cell every piece of every game stood on at its setup -- the labels of a
+    tracked replay of the games' action logs from their start records (replay(..., track_origins=True).origins).  `beliefs` is then read
+    as a prior over SETUP cells and carried along the moves (stratego_env_amd.beliefs.follow): one table per game.
     leaf: None = a playout cut off by max_steps counts 0; else (table, limit, denom) as PackedStates.set_leaf_values takes them
     (stratego_env_amd.leaf_values builds tables): the position a cut-off playout reached is scored by the table, on the sampled world's
     true pieces."""
@@ -38,6 +41,12 @@ def choose_moves(env, n_worlds=4, draw=0, seed=0, max_steps=0, weights=None, see
     children = None
     try:
         game_of_world = torch.arange(B, dtype=torch.int32, device=dev).repeat(W)
+        if origins is not None:
+            if beliefs is None:
+                raise ValueError("origins carry a prior over setup cells along the moves: pass beliefs")
+            from stratego_env_amd.beliefs import follow
+            prior = beliefs if isinstance(beliefs, torch.Tensor) else torch.from_numpy(beliefs.astype('int32'))
+            beliefs = follow(prior.to(dev), origins)                  # [B, 2, 12, cells]: the table of game b for every world of b
         if beliefs is None:
             worlds.determinize(env, src_index=game_of_world, observer=0, draw=draw)
         else:

@@ -480,18 +480,20 @@ class BatchedStrategoProceduralEnv:
         finally:
             src.close()
 
-    def replay(self, states, players, actions, lengths=None, skip_invalid=False, actions_1d=True, allow_piece_oscillation=False, return_states=True):
+    def replay(self, states, players, actions, lengths=None, skip_invalid=False, actions_1d=True, allow_piece_oscillation=False, return_states=True,
+               track_origins=False, origins_in=None):
         """Every state advanced by its list of actions, all moves in one launch (PackedStates.replay: pack -> replay into a scratch pool ->
         unpack, for callers on the reference layout).  actions: int32 [n, L]; absolute 1-D indices as get_next_state takes them
         (actions_1d=False: flat spatial indices in the mover's perspective); lengths: int32 [n] (None: L for all).
         -> (ReplayResult, states int64 [n,34,R,C], players int8 [n]); with return_states=False the ReplayResult alone.  The same as L calls
-        of get_next_state that stop at the end of the game and -- unless skip_invalid -- at the first invalid action."""
+        of get_next_state that stop at the end of the game and -- unless skip_invalid -- at the first invalid action.
+        track_origins / origins_in: as PackedStates.replay takes them; ReplayResult.origins then holds every piece's cell in `states`."""
         src = self.pack(states, players)
         try:
             dst = self.new_packed(src.n)
             try:
                 res = dst.replay(src, actions, lengths=lengths, skip_invalid=skip_invalid, actions_1d=actions_1d,
-                                 allow_piece_oscillation=allow_piece_oscillation)
+                                 allow_piece_oscillation=allow_piece_oscillation, track_origins=track_origins, origins_in=origins_in)
                 if not return_states:
                     return res
                 final, final_players = dst.unpack()
@@ -584,11 +586,14 @@ class PlayoutResult:
 class ReplayResult:
     """What replay reports per slot (device tensors): applied int32 (moves applied), consumed int32 (entries gone past, applied or
     skipped), stop uint8 (0 = the list was exhausted, 1 = the game was over, 2 = an invalid action: entry `consumed` is the offending one),
-    and, of the final position as for a playout, reward float32 [n,2], done uint8, ending_invalid uint8, player int8."""
+    and, of the final position as for a playout, reward float32 [n,2], done uint8, ending_invalid uint8, player int8.
+    origins: int16 [n, 2, cells] of a replay with track_origins (the root cell -- or the given label -- of the piece of player index p on
+    absolute cell c of the final position, -1 where it has none), else None."""
 
-    def __init__(self, applied, consumed, stop, reward, done, ending_invalid, player):
+    def __init__(self, applied, consumed, stop, reward, done, ending_invalid, player, origins=None):
         self.applied, self.consumed, self.stop = applied, consumed, stop
         self.reward, self.done, self.ending_invalid, self.player = reward, done, ending_invalid, player
+        self.origins = origins
 
     value_for = PlayoutResult.value_for
 
@@ -770,16 +775,21 @@ class PackedStates:
         vec._next_actions_fresh = False
         return res
 
-    def replay(self, src, actions, lengths=None, src_index=None, skip_invalid=False, actions_1d=False, allow_piece_oscillation=False):
+    def replay(self, src, actions, lengths=None, src_index=None, skip_invalid=False, actions_1d=False, allow_piece_oscillation=False,
+               track_origins=False, origins_in=None):
         """self[i] = src[src_index[i]] advanced by the list actions[i, :lengths[i]], every move in one launch (sgx_replay; the rule is in
         include/stratego_mi355x.h); `src` stays what it was.  `src`: a PackedStates (this pool itself for an in-place call without
         src_index) or a live VecStrategoEnv of the same variant.  actions: int32 device tensor [n, L] with any non-negative strides, taken
         as it is (the transposed [T, N] action log of a trajectory needs no copy); lengths int32 [n] (None: L for all).  skip_invalid: an
         invalid entry is passed over, else it ends the replay (stop == 2); actions_1d: absolute 1-D indices as `expand` takes them, else
         flat spatial indices in the mover's perspective as env.step() takes them.  -> ReplayResult.  (VecStrategoEnv.replay is the same
-        call with a live env as the destination.)"""
+        call with a live env as the destination.)
+        track_origins: ReplayResult.origins = int16 [n, 2, cells], the cell in `src` of every piece of the final position (-1 on cells
+        without one): piece identity, which the record does not carry -- beliefs.follow turns a setup prior into per-record belief tables
+        with it.  origins_in: int16 device tensor [src's n, 2, cells], labels the roots already carry (an earlier replay's origins, to
+        chain two replays; or any piece ids), carried verbatim."""
         return self._vec.replay(src, actions, lengths=lengths, src_index=src_index, skip_invalid=skip_invalid, actions_1d=actions_1d,
-                                allow_piece_oscillation=allow_piece_oscillation)
+                                allow_piece_oscillation=allow_piece_oscillation, track_origins=track_origins, origins_in=origins_in)
 
     def count_moves(self, index=None):
         """-> (counts int32 [n], offsets int64 [n + 1]): the valid moves of record index[i] (None: every record in order) and their exclusive

@@ -814,7 +814,8 @@ class VecStrategoEnv:
         self._next_actions_fresh = False
         return self.observe()
 
-    def replay(self, src, actions, lengths=None, src_index=None, skip_invalid=False, actions_1d=False, allow_piece_oscillation=False):
+    def replay(self, src, actions, lengths=None, src_index=None, skip_invalid=False, actions_1d=False, allow_piece_oscillation=False,
+               track_origins=False, origins_in=None):
         """Every game i of this env becomes src[src_index[i]] advanced by its list actions[i, :lengths[i]], all moves in one launch
         (sgx_replay; the rule is in include/stratego_mi355x.h); `src` stays what it was.  A following observe() renders the replayed
         positions' observations and masks: with start records and recorded actions a learner re-renders any (game, t) it samples instead
@@ -823,7 +824,13 @@ class VecStrategoEnv:
         src_index).  actions: int32 device tensor [n, L] with ANY non-negative strides, passed through as they are -- traj['actions'][:T].T
         is taken without a copy.  lengths: int32 [n] (None: L for all).  skip_invalid: an invalid entry is passed over instead of ending
         the replay; actions_1d: entries are absolute 1-D indices (get_next_state's) instead of flat spatial indices in the mover's
-        perspective.  No auto-reset: a replay stops at the end of its game.  -> ReplayResult."""
+        perspective.  No auto-reset: a replay stops at the end of its game.  -> ReplayResult.
+        track_origins: the same replay also tracks every piece back to the cell it stood on in `src` (sgx_set_replay_origins; the rule is in
+        the header): ReplayResult.origins is int16 [n, 2, cells], origins[i][p][c] = the root cell of the piece of player index p (0 = +1,
+        1 = -1) on absolute cell c of the final position, -1 where it has none -- what beliefs.follow takes.  origins_in (implies
+        track_origins): an int16 device tensor [src's n, 2, cells] of labels the roots already carry (the origins of an earlier replay, or
+        any piece ids), read at record src_index[i] and carried verbatim instead of the cells' own indices.  Every other result, and the
+        records, are what the untracked call gives."""
         from .procedural_env import ReplayResult
         n, dev = self.num_envs, self.device
         src_vec = getattr(src, '_vec', src)
@@ -853,8 +860,24 @@ class VecStrategoEnv:
         io = _lib.SgxReplayIO(a.data_ptr() if L else None, _ptr(ln), res.applied.data_ptr(), res.consumed.data_ptr(), res.stop.data_ptr(),
                               res.reward.data_ptr(), res.done.data_ptr(), res.ending_invalid.data_ptr(), res.player.data_ptr(),
                               game_stride, step_stride, elems, L, flags)
-        with torch.cuda.device(dev):
-            _lib.check(self._L.sgx_replay(self._h, src_vec._h, _ptr(si), C.byref(io), self._stream()), self._L)
+        if origins_in is not None:
+            cells = self.R * self.Cc
+            if not isinstance(origins_in, torch.Tensor) or origins_in.dtype != torch.int16 or origins_in.device != dev or not origins_in.is_contiguous() \
+                    or tuple(origins_in.shape) != (src_vec.num_envs, 2, cells):
+                raise ValueError("origins_in must be a contiguous int16 device tensor [%d, 2, %d] (one block of labels per record of src)"
+                                 % (src_vec.num_envs, cells))
+            track_origins = True
+        if not track_origins:
+            with torch.cuda.device(dev):
+                _lib.check(self._L.sgx_replay(self._h, src_vec._h, _ptr(si), C.byref(io), self._stream()), self._L)
+        else:
+            res.origins = torch.empty((n, 2, self.R * self.Cc), dtype=torch.int16, device=dev)
+            _lib.check(self._L.sgx_set_replay_origins(self._h, _ptr(origins_in), res.origins.data_ptr()), self._L)
+            try:
+                with torch.cuda.device(dev):
+                    _lib.check(self._L.sgx_replay(self._h, src_vec._h, _ptr(si), C.byref(io), self._stream()), self._L)
+            finally:                                                 # the setting lasts for this call alone, also when it raises
+                self._L.sgx_set_replay_origins(self._h, None, None)
         self._next_actions_fresh = False
         return res
 

@@ -1,0 +1,341 @@
+"""Piece origins on the GPU (sgx_set_replay_origins, the TRACK instantiations of the replay kernel): the labels bit for bit those
+of the numpy restatement of the rule on the oracle (tests/origins_rule.py, which tests/test_origins_cpu.py holds to known answers), on
+every geometry class of the family -- four and two games per wave, an odd board, the half-wave variant, 225 cells -- with ragged lists
+that cross the prefetch chunks in both layouts, through an index and in place; every other byte of the call against the untracked call;
+chaining and given labels; the golden games with the labels' invariants from device outputs alone; guard bands; the refusals; and the loop
+the feature closes: trajectory -> tracked replay -> beliefs.follow -> weighted determinization.
+
+Every slot of every launch is compared.  The restated moves of a test stay under about 60,000."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from tests import origins_rule as orr
+from tests.test_gpu_playout import CASES, N_SRC, _np, _roots
+from tests.test_gpu_replay import GOLDEN, LPG, _golden, _golden_roots, _layouts, _ragged_lists, _results
+
+pytestmark = pytest.mark.gpu
+
+SGX_EINVAL = -1
+BOARDS = ['micro', 'fives', 'medium', 'barrage', 'standard2']
+N_SLOTS = 29                                       # not a multiple of any games-per-workgroup
+
+
+@functools.lru_cache(None)
+def _material(name):
+    """The roots (as tests/test_gpu_playout._roots takes them), an index with repeats and the ragged lists of its slots: numpy only, made
+    once per board.  The env is made again by every test (same seed, same games)."""
+    env, states, players, finished = _roots(name, CASES[name][0])
+    env.close()
+    rs = np.random.RandomState(23)
+    idx = rs.randint(0, N_SRC, size=N_SLOTS).astype(np.int32)
+    idx[:8] = CASES[name][2]                       # eight slots of one unfinished root, wave-mates among them
+    sp, d1, lengths = _ragged_lists(name, states, players, idx, rs)
+    cells = states[0][0].size
+    given = rs.randint(-32768, 32768, size=(N_SRC, 2, cells)).astype(np.int16)
+    given[:, :, ::5] = -1                          # -1 is a label like any other
+    return states, players, finished, idx, sp, d1, lengths, given
+
+
+def _record_bytes(pool):
+    """everything a record holds, as the library exports it: the 34 layers, the mover, and the counters"""
+    st, pl = pool.unpack()
+    return [_np(st).tobytes(), _np(pl).tobytes(), _np(pool._vec.env_info()).tobytes()]
+
+
+def _same_but_for_the_labels(tracked_pool, tracked, plain_pool, plain, where):
+    a, b = _results(tracked), _results(plain)
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), (where, k)
+    assert _record_bytes(tracked_pool) == _record_bytes(plain_pool), where
+
+
+# ---- A: bit for bit the rule, and no other byte changes ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', BOARDS)
+def test_labels_are_the_rules_on_ragged_lists(name):
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    states, players, finished, idx, sp, d1, lengths, given = _material(name)
+    env = _roots(name, CASES[name][0])[0]
+    assert finished.any() and not finished.all()
+    assert int(lengths.max()) == 2 * LPG[name] + 3 and (lengths == 0).any()
+    idx_t, lengths_t, given_t = torch.from_numpy(idx).cuda(), torch.from_numpy(lengths).cuda(), torch.from_numpy(given).cuda()
+    before = [t.clone() for t in env.export_state()]
+    tracked, plain = PackedStates(name, N_SLOTS, seed=3), PackedStates(name, N_SLOTS, seed=3)
+    moves, wave_mates_differ, stops = 0, False, set()
+    modes = [(sp, dict(skip_invalid=False)), (sp, dict(skip_invalid=True)), (d1, dict(skip_invalid=False, actions_1d=True)),
+             (d1, dict(skip_invalid=True, actions_1d=True))]
+    for acts, flags in modes:
+        want = orr.replay_tracked_batch(name, states, players, acts, lengths, idx, **flags)
+        for layout, view, whole in _layouts(acts, torch):
+            where = (name, layout, sorted(flags.items()))
+            res = tracked.replay(env, view, lengths=lengths_t, src_index=idx_t, track_origins=True, **flags)
+            assert tracked.last_launch_kind == _lib.LAUNCH_REPLAY_TRACKED == 8, where
+            assert res.origins.dtype == torch.int16 and tuple(res.origins.shape) == want.shape
+            assert _np(res.origins).tobytes() == want.tobytes(), (where, np.argwhere(_np(res.origins) != want)[:5].tolist())
+            res0 = plain.replay(env, view, lengths=lengths_t, src_index=idx_t, **flags)
+            assert plain.last_launch_kind == _lib.LAUNCH_REPLAY == 5 and res0.origins is None
+            _same_but_for_the_labels(tracked, res, plain, res0, where)
+        consumed = _np(res.consumed)
+        moves += int(consumed.sum())
+        stops |= set(_np(res.stop).tolist())
+        wave_mates_differ |= bool((consumed[0:-1:2] != consumed[1::2]).any())
+    # given labels through the index: carried verbatim
+    want = orr.replay_tracked_batch(name, states, players, sp, lengths, idx, skip_invalid=True, origins_in=given)
+    res = tracked.replay(env, torch.from_numpy(sp).cuda(), lengths=lengths_t, src_index=idx_t, skip_invalid=True, origins_in=given_t)
+    assert tracked.last_launch_kind == _lib.LAUNCH_REPLAY_TRACKED
+    assert _np(res.origins).tobytes() == want.tobytes()
+    assert torch.equal(given_t, torch.from_numpy(given).cuda())
+    moves += int(_np(res.consumed).sum())
+    # the wrapper has cleared the setting: the untracked call on the same pool is the untracked call again
+    assert not tracked._vec._L.sgx_replay_origins_set(tracked._vec._h)
+    res1 = tracked.replay(env, torch.from_numpy(sp).cuda(), lengths=lengths_t, src_index=idx_t, skip_invalid=True)
+    res0 = plain.replay(env, torch.from_numpy(sp).cuda(), lengths=lengths_t, src_index=idx_t, skip_invalid=True)
+    assert tracked.last_launch_kind == _lib.LAUNCH_REPLAY and res1.origins is None
+    _same_but_for_the_labels(tracked, res1, plain, res0, (name, 'after clearing'))
+    after = env.export_state()
+    assert torch.equal(after[0], before[0]) and torch.equal(after[1], before[1])
+    assert stops == {0, 1, 2} and wave_mates_differ, (stops, wave_mates_differ)
+    print(name, 'restated entries', moves)
+    assert moves < 60000
+    for x in (tracked, plain, env):
+        x.close()
+
+
+@pytest.mark.parametrize('name', BOARDS)
+def test_with_a_leaf_table_tracking_changes_no_other_byte(name):
+    import torch
+    from stratego_env_amd import _lib, leaf_values
+    from stratego_env_amd.procedural_env import PackedStates
+    states, players, finished, idx, sp, d1, lengths, given = _material(name)
+    env = _roots(name, CASES[name][0])[0]
+    idx_t, lengths_t, acts_t = torch.from_numpy(idx).cuda(), torch.from_numpy(lengths).cuda(), torch.from_numpy(sp).cuda()
+    tracked, plain = PackedStates(name, N_SLOTS, seed=3), PackedStates(name, N_SLOTS, seed=3)
+    want = orr.replay_tracked_batch(name, states, players, sp, lengths, idx, skip_invalid=True)
+    denom = 2 * leaf_values.side_total(name)
+    table = leaf_values.with_advance(leaf_values.material(name), 1, rows=env.variant.rows)
+    for pool in (tracked, plain):
+        pool.set_leaf_values(table, denom - 1, denom)
+    res = tracked.replay(env, acts_t, lengths=lengths_t, src_index=idx_t, skip_invalid=True, track_origins=True)
+    res0 = plain.replay(env, acts_t, lengths=lengths_t, src_index=idx_t, skip_invalid=True)
+    assert tracked.last_launch_kind == _lib.LAUNCH_REPLAY_TRACKED and plain.last_launch_kind == _lib.LAUNCH_REPLAY
+    assert _np(res.origins).tobytes() == want.tobytes()
+    _same_but_for_the_labels(tracked, res, plain, res0, (name, 'leaf'))
+    live = _np(res.done) == 0
+    assert live.any() and (_np(res.reward)[live] != 0).any(), "the leaf table was in use"
+    # a copy-only call writes the start labels
+    res = tracked.replay(env, acts_t[:, :0], src_index=idx_t, track_origins=True)
+    assert _np(res.origins).tobytes() == np.stack([orr.start_labels(states[s]) for s in idx]).tobytes()
+    for x in (tracked, plain, env):
+        x.close()
+
+
+# ---- B: chaining on the device, in place -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['fives', 'barrage'])
+def test_two_halves_chained_in_place_equal_one_pass(name):
+    import torch
+    from stratego_env_amd.procedural_env import PackedStates
+    states, players, finished, idx, sp, d1, lengths, given = _material(name)
+    env = _roots(name, CASES[name][0])[0]
+    idx_t, given_t = torch.from_numpy(idx).cuda(), torch.from_numpy(given).cuda()
+    half = lengths // 2
+    second = np.zeros_like(sp)
+    for i in range(N_SLOTS):
+        second[i, :lengths[i] - half[i]] = sp[i, half[i]:lengths[i]]
+    pool, whole = PackedStates(name, N_SLOTS), PackedStates(name, N_SLOTS)
+    L, h = pool._vec._L, pool._vec._h
+    for origins_in, origins_in_np in ((None, None), (given_t, given)):
+        want = orr.replay_tracked_batch(name, states, players, sp, lengths, idx, skip_invalid=True, origins_in=origins_in_np)
+        one = whole.replay(env, torch.from_numpy(sp).cuda(), lengths=torch.from_numpy(lengths).cuda(), src_index=idx_t, skip_invalid=True,
+                           track_origins=True, origins_in=origins_in)
+        assert _np(one.origins).tobytes() == want.tobytes()
+        first = pool.replay(env, torch.from_numpy(sp).cuda(), lengths=torch.from_numpy(half).cuda(), src_index=idx_t, skip_invalid=True,
+                            track_origins=True, origins_in=origins_in)
+        labels = first.origins
+        # the second half in place: the pool onto itself, and the labels onto themselves (origin_in == origin_out, no index)
+        assert L.sgx_set_replay_origins(h, C.c_void_p(labels.data_ptr()), C.c_void_p(labels.data_ptr())) == 0, L.sgx_last_error()
+        try:
+            assert L.sgx_replay_origins_set(h) == 1
+            rest = pool.replay(pool, torch.from_numpy(second).cuda(), lengths=torch.from_numpy(lengths - half).cuda(), skip_invalid=True)
+        finally:
+            assert L.sgx_set_replay_origins(h, None, None) == 0
+        assert L.sgx_replay_origins_set(h) == 0
+        assert _np(labels).tobytes() == want.tobytes()
+        assert _record_bytes(pool) == _record_bytes(whole)
+        assert np.array_equal(_np(first.applied) + _np(rest.applied), _np(one.applied))
+    for x in (pool, whole, env):
+        x.close()
+
+
+# ---- C: the golden games of each variant in one launch; the invariants from device outputs alone ----------------------------------------------
+@pytest.mark.parametrize('name', GOLDEN)
+def test_golden_games_keep_the_labels_invariants(name):
+    import torch
+    from stratego_env_amd.procedural_env import PackedStates
+    g, acts, lengths, errs = _golden(name)
+    n = len(lengths)
+    env = _golden_roots(name, g)
+    pool = PackedStates(name, n)
+    res = pool.replay(env, torch.from_numpy(acts).cuda(), lengths=torch.from_numpy(lengths).cuda(), skip_invalid=True, track_origins=True)
+    start, final, lab = env.export_state()[0], pool.unpack()[0], res.origins.long()
+    assert torch.equal(final, torch.from_numpy(g['final_states'][:n].astype(np.int64)).cuda())
+    cells = lab.shape[2]
+    moved = 0
+    for q in range(2):
+        own_start, own_final, l = start[:, q].reshape(n, cells), final[:, q].reshape(n, cells), lab[:, q]
+        occ = own_final != 0
+        assert torch.equal(l != -1, occ), "a label exactly where a piece stands"
+        assert bool(((l >= 0) & (l < cells))[occ].all())
+        # injective: the labels of a game's occupied cells, scattered as counts over the cells, never meet
+        counts = torch.zeros((n, cells + 1), dtype=torch.int64, device=l.device)
+        counts.scatter_add_(1, torch.where(occ, l, torch.full_like(l, cells)), occ.long())
+        assert int(counts[:, :cells].max()) <= 1, "no label twice"
+        types = torch.gather(own_start, 1, l.clamp(min=0))
+        assert torch.equal(types[occ], own_final[occ]), "a piece is of the type that started on the cell its label names"
+        moved += int((l[occ] != torch.arange(cells, device=l.device).expand(n, cells)[occ]).sum())
+    assert moved > 0
+    pool.close(); env.close()
+
+
+# ---- D: guard bands -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['fives', 'barrage'])
+def test_guard_bands_around_the_labels(name):
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    from tests.test_gpu_guard_bands import Arena
+    states, players, finished, idx, sp, d1, lengths, given = _material(name)
+    env = _roots(name, CASES[name][0])[0]
+    cells = states[0][0].size
+    pool = PackedStates(name, N_SLOTS)
+    vec = pool._vec
+    L = vec._L
+    idx_t, lengths_t, acts_t = torch.from_numpy(idx).cuda(), torch.from_numpy(lengths).cuda(), torch.from_numpy(sp).cuda()
+    keep_idx, keep_acts = idx_t.clone(), acts_t.clone()
+    src_before = [t.clone() for t in env.export_state()]
+    Lmax = sp.shape[1]
+    io = _lib.SgxReplayIO(acts_t.data_ptr(), lengths_t.data_ptr(), None, None, None, None, None, None, None, Lmax, 1, N_SLOTS * Lmax, Lmax,
+                          _lib.REPLAY_SKIP_INVALID)                                   # every result pointer NULL
+    want = {False: orr.replay_tracked_batch(name, states, players, sp, lengths, idx, skip_invalid=True),
+            True: orr.replay_tracked_batch(name, states, players, sp, lengths, idx, skip_invalid=True, origins_in=given)}
+    for phase in (0, 4, 8, 12):
+        for with_in in (False, True):
+            out = Arena('origin_out', (N_SLOTS, 2, cells), torch.int16, phase, vec.device)
+            inp = Arena('origin_in', (N_SRC, 2, cells), torch.int16, (phase + 4) % 16, vec.device)
+            inp.t.copy_(torch.from_numpy(given))
+            assert L.sgx_set_replay_origins(vec._h, C.c_void_p(inp.t.data_ptr()) if with_in else None, C.c_void_p(out.t.data_ptr())) == 0, L.sgx_last_error()
+            try:
+                assert L.sgx_replay(vec._h, env._h, C.c_void_p(idx_t.data_ptr()), C.byref(io), vec._stream()) == 0, L.sgx_last_error()
+                torch.cuda.synchronize()
+            finally:
+                assert L.sgx_set_replay_origins(vec._h, None, None) == 0
+            assert L.sgx_last_launch_kind(vec._h) == _lib.LAUNCH_REPLAY_TRACKED
+            out.check_guards('sgx_replay tracked')
+            out.check_written('sgx_replay tracked')
+            assert out.host().tobytes() == want[with_in].tobytes(), (name, phase, with_in)
+            inp.check_guards('sgx_replay tracked')
+            assert np.array_equal(inp.host(), given)
+    after = env.export_state()
+    assert torch.equal(after[0], src_before[0]) and torch.equal(after[1], src_before[1])
+    assert torch.equal(idx_t, keep_idx) and torch.equal(acts_t, keep_acts)
+    pool.close(); env.close()
+
+
+# ---- E: refusals ---------------------------------------------------------------------------------------------------------------------------------
+def test_refusals_are_host_side():
+    import torch
+    from stratego_env_amd import _lib
+    from stratego_env_amd.procedural_env import PackedStates
+    name, n = 'fives', 16
+    env = _roots(name, 4, n=n)[0]
+    pool = PackedStates(name, n)
+    pool.copy_from(env)
+    vec = pool._vec
+    L, h = vec._L, vec._h
+    cells = 25
+    per = 2 * cells
+    buf = torch.full((3 * n * per,), 77, dtype=torch.int16, device='cuda')
+    acts = torch.zeros((n, 2), dtype=torch.int32, device='cuda')
+    idx = torch.arange(n, dtype=torch.int32, device='cuda')
+    outs = torch.full((n,), 77, dtype=torch.int32, device='cuda')
+    io = _lib.SgxReplayIO(acts.data_ptr(), None, outs.data_ptr(), None, None, None, None, None, None, 2, 1, 2 * n, 2, _lib.REPLAY_SKIP_INVALID)
+    records = _record_bytes(pool)
+    base = buf.data_ptr()
+
+    def refused_replay(in_off, out_off, index, *words):
+        assert L.sgx_set_replay_origins(h, C.c_void_p(base + 2 * in_off), C.c_void_p(base + 2 * out_off)) == 0, L.sgx_last_error()
+        rc = L.sgx_replay(h, env._h, C.c_void_p(idx.data_ptr()) if index else None, C.byref(io), vec._stream())
+        msg = L.sgx_last_error().decode()
+        assert L.sgx_set_replay_origins(h, None, None) == 0
+        assert rc == SGX_EINVAL and all(w in msg for w in ('sgx_replay', 'origin_in_dev', 'origin_out_dev') + words), (rc, msg)
+
+    refused_replay(0, 0, True, 'index')                                  # equal, with an index
+    refused_replay(0, n * per - 2, True, 'index')                        # the last two elements of in are the first two of out
+    refused_replay(n * per - 2, 0, True, 'index')
+    refused_replay(0, per, False, 'overlap')                             # shifted by one game
+    refused_replay(per, 0, False, 'overlap')
+    refused_replay(0, n * per - 2, False, 'overlap')
+    # misalignment: the setter's own refusal, the setting stays what it was
+    for in_off, out_off, which in ((0, 1, 'origin_out_dev'), (1, n * per, 'origin_in_dev')):
+        assert L.sgx_set_replay_origins(h, C.c_void_p(base + 2 * in_off), C.c_void_p(base + 2 * out_off)) == SGX_EINVAL
+        msg = L.sgx_last_error().decode()
+        assert 'sgx_set_replay_origins' in msg and which in msg and '4-byte aligned' in msg, msg
+        assert L.sgx_replay_origins_set(h) == 0
+    assert L.sgx_set_replay_origins(None, None, C.c_void_p(base)) == SGX_EINVAL and b'sgx_set_replay_origins' in L.sgx_last_error()
+    torch.cuda.synchronize()
+    assert bool((buf == 77).all()) and bool((outs == 77).all()), "nothing ran"
+    assert _record_bytes(pool) == records
+    # what is legal next to it: disjoint ranges with an index, and equal pointers without one
+    assert L.sgx_set_replay_origins(h, C.c_void_p(base), C.c_void_p(base + 2 * n * per)) == 0
+    assert L.sgx_replay(h, env._h, C.c_void_p(idx.data_ptr()), C.byref(io), vec._stream()) == 0, L.sgx_last_error()
+    assert L.sgx_set_replay_origins(h, C.c_void_p(base), C.c_void_p(base)) == 0
+    assert L.sgx_replay(h, env._h, None, C.byref(io), vec._stream()) == 0, L.sgx_last_error()
+    assert L.sgx_set_replay_origins(h, None, None) == 0
+    torch.cuda.synchronize()
+    pool.close(); env.close()
+
+
+# ---- F: end to end -- trajectory -> tracked replay -> follow -> weighted determinization ------------------------------------------------------
+def test_a_followed_one_hot_prior_deals_the_truth_back():
+    import torch
+    from stratego_env_amd import beliefs
+    from stratego_env_amd.procedural_env import PackedStates
+    from stratego_env_amd.vec_env import VecStrategoEnv
+    name, N, T = 'barrage', 64, 100
+    env = VecStrategoEnv(name, N, seed=29, auto_reset=False, placement='plain')
+    env.reset()
+    start, now, worlds = PackedStates(name, N), PackedStates(name, N), PackedStates(name, N, seed=5)
+    start.copy_from(env)
+    log = torch.empty((T, N), dtype=torch.int32, device='cuda')
+    for t in range(T):                                   # (a finished game gets an out-of-range entry, which leaves it untouched)
+        over = env.env_info()[:, 2] != 0
+        drawn = env.sample_valid_actions()
+        log[t] = torch.where(over, torch.full_like(drawn, -1), drawn)
+        env.step(log[t], emit_obs=False)
+    res = now.replay(start, log.T, track_origins=True)                       # the [T, N] log as it is
+    assert torch.equal(now.unpack()[0], env.export_state()[0])
+    start_state, state = start.unpack()[0], now.unpack()[0]
+    cells = 100
+    observer = 1
+    # the prior is per record: one-hot on each game's START position (both players' blocks; the deal reads the observer's opponent's)
+    own = start_state[:, :2].reshape(N, 2, 1, cells)
+    prior = (own == torch.arange(1, 13, device='cuda').view(1, 1, 12, 1)).to(torch.int32) * 4095
+    followed = beliefs.follow(prior, res.origins)
+    assert tuple(followed.shape) == (N, 2, 12, cells) and followed.dtype == torch.int32
+    # precondition: a hidden piece of the observer's opponent stands off its start cell
+    opp = 1
+    hidden_cell = (state[:, opp].reshape(N, cells) != 0) & (state[:, 3 + opp].reshape(N, cells) == 13)
+    off_start = hidden_cell & (res.origins[:, opp].long() != torch.arange(cells, device='cuda'))
+    assert bool(off_start.any()), "no hidden opponent piece has moved: the test would show nothing"
+    hidden, off = worlds.determinize(now, observer=observer, draw=7, beliefs=followed, return_off_belief=True)
+    assert bool((hidden >= 0).all()) and bool((hidden > 0).any())
+    assert bool((off == 0).all()), "every hidden piece was dealt onto a cell its followed belief allows"
+    assert _record_bytes(worlds) == _record_bytes(now), "a one-hot belief on the truth deals the truth back"
+    # control: the same prior unfollowed knows nothing of the moves
+    hidden2, off2 = worlds.determinize(now, observer=observer, draw=7, beliefs=prior, return_off_belief=True)
+    assert bool((off2[off_start.any(dim=1)] > 0).any())
+    for x in (start, now, worlds, env):
+        x.close()

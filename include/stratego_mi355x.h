@@ -236,7 +236,10 @@ int sgx_build_original_obs_lut(const sgx_config *cfg, int32_t full, float *lut);
  * A limit of the key: the RNG's first mix takes seed + 0x9E3779B97F4A7C15 * (global id + 1), so (seed, g) and
  * (seed + 0x9E3779B97F4A7C15, g - 1) name the same stream: two handles whose seeds differ by exactly that constant (mod 2^64) play the
  * same games shifted by one env id.  Seeds that differ by anything else -- s + 1, s + (1 << 32) -- give independent games
- * (tests/test_draws_cpu.py, tests/test_gpu_draws.py).  The arithmetic stays as it is: recorded trajectories are keyed on it. */
+ * (tests/test_draws_cpu.py, tests/test_gpu_draws.py).  The arithmetic stays as it is: recorded trajectories are keyed on it.
+ * n_envs must lie in [1, 2^30]: anything else is SGX_EINVAL before the device is touched.  The bound is what keeps every 32-bit
+ * quantity of a launch in range -- the grid size, the XCD shares xcd_first / xcd_count, one workgroup per game in sgx_reset and
+ * sgx_sample_valid; the byte offsets of games, slots, records and lists are 64-bit everywhere (tests/test_gpu_big_offsets.py). */
 int sgx_create(const sgx_config *cfg, int64_t n_envs, int device, uint64_t seed, int64_t env_id_offset, sgx_env **out);
 int sgx_destroy(sgx_env *h);
 
@@ -591,6 +594,7 @@ int sgx_set_general_states(sgx_env *h, int32_t mode);
  * no fully-observable / original-channel outputs); src == dst with a NULL index is sgx_step.  Inside ONE handle an indexed
  * copy / expansion would race (a wave reads a record another wave of the same launch rewrites): sgx_expand with src == dst and
  * a non-NULL index, and sgx_copy_envs with src == dst and any index, return SGX_EINVAL -- use a second handle as the target.
+ * sgx_copy_envs: n in [0, 2^31), else SGX_EINVAL before any launch (with two index arrays no handle's size bounds it).
  * No reference counterpart beyond get_next_state itself. */
 int sgx_copy_envs(sgx_env *dst, const int32_t *dst_index_dev, sgx_env *src, const int32_t *src_index_dev, int64_t n, void *stream);
 int sgx_expand(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_step_io *io, void *stream);

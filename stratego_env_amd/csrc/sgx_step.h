@@ -702,7 +702,14 @@ __device__ __forceinline__ void env_step(const KP &P, Lds<Geo<R_, C_, VAR>, ObsK
             int4 *mdst = reinterpret_cast<int4 *>(reinterpret_cast<uint32_t *>(io_mask) + env * (int64_t)G::MB_WORDS);
             for (int i = lane; i < G::MB_WORDS / 4; i += G::LPG) mdst[i] = reinterpret_cast<const int4 *>(L.mbits)[i];
         }
+#ifdef SGX_MUTANT_OFFSET32
+        // test-the-tests build (tools/mutant_check.sh, off in every shipped build): the per-step kernel's byte offset of a game's mask
+        // truncated to uint32.  The wrapped offset is SMALLER than the right one: the store stays inside the caller's tensor (a wrong
+        // byte, never a fault) and differs only where env * NA reaches 2^32 -- tests/test_gpu_big_offsets.py has to notice.
+        else emit_mask(L, io_mask + (PERSIST ? env * (int64_t)NA : (int64_t)(uint32_t)(env * (int64_t)NA)), lane);
+#else
         else emit_mask(L, io_mask + env * (int64_t)NA, lane);
+#endif
     }
     STAMP(5);   // mask stores issued
     // (rendering the observation before the mask, so that its stores drain during mask generation, measured 6 % slower)

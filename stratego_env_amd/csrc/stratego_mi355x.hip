@@ -2184,6 +2184,8 @@ SGX_API int sgx_copy_envs(sgx_env *dst, const int32_t *dst_index_dev, sgx_env *s
     if (!dst || !src) return fail(SGX_EINVAL, "handle is NULL%s");
     if (int rc = same_variant(dst, src)) return rc;
     if (n < 0 || (!dst_index_dev && n > dst->n_envs) || (!src_index_dev && n > src->n_envs)) return fail(SGX_EINVAL, "n out of range%s");
+    // (with both index arrays nothing else bounds n: the grid is a 32-bit count of (n + 3) / 4 workgroups)
+    if (n > 0x7fffffff) return fail(SGX_EINVAL, "sgx_copy_envs: n must be in [0, 2^31)%s");
     // inside one pool a wave may read a record another wave of the same launch rewrites: only the identity copy is race-free
     if (dst == src && (dst_index_dev || src_index_dev))
         return fail(SGX_EINVAL, "sgx_copy_envs: an indexed copy inside one handle would race; stage through a second handle%s");

@@ -48,7 +48,8 @@ extern "C" {
 
 #define SGX_ABI_VERSION 15       /* (sgx_count_moves, sgx_expand_all and sgx_children_io are additions within v15: new entry points and a new
                                     struct, no existing layout or signature changed; sgx_playout_weighted is an addition within v15 too:
-                                    a new entry point on sgx_playout_io as it is; so is sgx_determinize_weighted) */
+                                    a new entry point on sgx_playout_io as it is; so is sgx_determinize_weighted; so are sgx_step_vs and
+                                    its sgx_vs_io) */
 #define SGX_MAX_CELLS 1024       /* rows*cols <= 1024 (largest reference variant: 15x15 = 225; the reference's StrategoProceduralEnv
                                     takes any size, penv:27-36: boards of more than 256 cells use 10-bit cell indices in the record) */
 #define SGX_PO_OBS_CHANNELS 67   /* impl:1332 */
@@ -148,6 +149,8 @@ typedef struct sgx_step_io {
  *   sgx_playout                  src_index_dev, reward_dev, length_dev 4; done_dev, ending_invalid_dev, player_dev 1
  *   sgx_playout_weighted         as sgx_playout; `weights` is HOST memory, read before the call returns (any uint16_t alignment): the
  *                                contract has nothing to add for it
+ *   sgx_step_vs                  src_index_dev, actions_dev, reward_dev, reply_action_dev 4; agent_dev, done_dev, ending_invalid_dev, player_dev,
+ *                                invalid_action_dev, moved_dev 1; `weights` is HOST memory, as for sgx_playout_weighted
  *   sgx_replay                   src_index_dev, actions_dev, lengths_dev, applied_dev, consumed_dev, reward_dev 4; stop_dev, done_dev, ending_invalid_dev, player_dev 1
  *   sgx_set_replay_origins       origin_in_dev, origin_out_dev 4 (their elements are read and written as 2-byte values; an odd board's rows
  *                                start at any 2-byte phase from there)
@@ -306,6 +309,7 @@ int sgx_set_steps_barrier(sgx_env *h, int32_t mode);
 #define SGX_LAUNCH_CHILDREN 6    /* sgx_expand_all: one wave per child, root found from the offsets, mask regenerated, move applied (set on dst) */
 #define SGX_LAUNCH_PLAYOUT_WEIGHTED 7   /* sgx_playout_weighted: sgx_playout's launch with the weighted draw (set on dst) */
 #define SGX_LAUNCH_REPLAY_TRACKED 8      /* sgx_replay while dst has sgx_set_replay_origins set: sgx_replay's launch, with the piece labels (set on dst) */
+#define SGX_LAUNCH_STEP_VS 9             /* sgx_step_vs: one wave per game, the agent's move and the bot's reply in one launch (set on dst) */
 int sgx_last_launch_kind(const sgx_env *h);
 
 /* Shares of the eight XCDs in a launch of sgx_step / sgx_observe.  Under a saturating write stream the odd XCDs of MI355X drain their
@@ -727,6 +731,59 @@ int sgx_playout(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const 
 #define SGX_PLAYOUT_WEIGHT_MAX 4095
 int sgx_playout_weighted(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_playout_io *io,
                          const uint16_t *weights /* HOST memory, [4][13][14] */, int32_t policy_flags, uint64_t draw, void *stream);
+
+/* Play against a built-in opponent: the agent's move and the reply of a table bot -- the policy of sgx_playout_weighted playing one side of
+ * a LIVE game -- in ONE launch that writes no observation: an agent decision against a fixed opponent costs one sgx_observe, not the two
+ * full steps of a host loop that merges two action sources.  N = dst's number of envs.  THE RULE (tests/step_vs_rule.py restates it on
+ * the CPU oracle, bit for bit):
+ *   For slot i of dst: pos = record src_index[i] of src (i when the index is NULL), side = the agent's side (agent_dev[i] < 0: -1, else
+ *   +1; `agent` when agent_dev is NULL), g = dst's env_id_offset + i.
+ *   1. invalid = moved = 0, reply = -1.
+ *   2. If pos is not over, its mover is `side` and actions_dev is given: actions_dev[i] is applied to pos exactly as sgx_step applies an
+ *      action -- the same decode (flat spatial index in the mover's perspective), the same validity checks (an out-of-range value, a move
+ *      the rules refuse, the no-op of a mover that has a move), the same endings; no auto-reset.  Refused: invalid = 1, pos stays what
+ *      it was, go to 4.  Applied: moved |= SGX_VS_MOVED_AGENT.  (Where the mover is not `side` the entry is not read as a move.)
+ *   3. If pos is not over and its mover is not `side`, the bot moves once: the valid moves a_0 < ... < a_{n-1}, dir, t, d, w_i and W are
+ *      those of sgx_playout_weighted's rule, taken for the bot as the mover, in the public view -- the bot does not cheat -- or with
+ *      SGX_VS_SEE_ALL the true one; r = rng(dst's seed, g, draw, STREAM_REPLY = 8, pos's turn counter).  n == 0: the no-op.  W > 0:
+ *      x = rng_below(r, W), the first a_i whose inclusive prefix sum exceeds x.  W == 0: the rng_below(r, n)-th valid move.  The move is
+ *      applied as a step applies it; reply = that action, moved |= SGX_VS_MOVED_BOT.  Players alternate, so there is never a second bot
+ *      move: the rule has no loop.
+ *   4. dst[i] = pos, whole.  reward / done / ending_invalid / player are what a step on that position reports, as sgx_playout words it: a
+ *      finished position reports its result on every call.
+ * Consequences (all tested): after the call every slot that is not over and not `invalid` has `side` to move; a slot that was over is
+ * copied, whatever its action; actions_dev == NULL is "the bot opens where it is its turn", every other slot a copy; a table whose
+ * entries are all the same constant c >= 1 draws uniformly over the bot's valid moves; a move of weight 0 is never drawn while another
+ * valid move has a weight > 0.
+ * STREAM_REPLY is a stream of its own: no existing draw moves.  `draw` stands where the rollouts' key has the game number: a caller that
+ * steps a live env passes another draw with every call (the same call gives the same replies).  src == dst with a NULL index works in
+ * place -- the live-env call (a game's record is read whole before it is written); with an index it would race and is SGX_EINVAL.  Also
+ * SGX_EINVAL, before anything is launched, under this function's name: everything sgx_playout_weighted refuses (weights == NULL, an entry
+ * above 4095, NULL handles or io, handles of different variants or devices, a NULL index with src smaller than dst, a misaligned
+ * src_index_dev or reward_dev) EXCEPT a start pool on dst; `agent` outside {+1, -1} with agent_dev == NULL; unknown flags bits;
+ * actions_dev or reply_action_dev not 4-byte aligned.  A dst with a start pool set IS accepted (a curriculum env is the main customer):
+ * the call never restarts a game and writes no start index; restarts are the caller's sgx_reset.  Leaf values set on dst are not used:
+ * this is live stepping, like sgx_step.  Asynchronous on `stream`; `weights` is HOST memory, read before the call returns, so two calls
+ * on one stream with different tables each play with their own.  Sets dst's sgx_last_launch_kind to SGX_LAUNCH_STEP_VS.  An addition
+ * within v15: no existing struct or signature changed, SGX_ABI_VERSION stays.
+ * Reference counterpart: the vs_bot branch of StrategoMultiAgentEnv (maenv:573-619), whose opponent is an external bot behind a socket. */
+#define SGX_VS_SEE_ALL 1           /* flags: the bot looks at the agent's TRUE types (as SGX_PLAYOUT_SEE_ALL); default: the public view */
+#define SGX_VS_MOVED_AGENT 1       /* bits of moved_dev */
+#define SGX_VS_MOVED_BOT   2
+typedef struct sgx_vs_io {
+    const int32_t *actions_dev;    /* [N] nullable: the agent's action, flat spatial index in the mover's perspective, as sgx_step takes it */
+    const int8_t  *agent_dev;      /* [N] nullable: the agent's side per slot, < 0 = player -1, else +1; NULL = `agent` for every slot */
+    float   *reward_dev;           /* [N,2] out, nullable: rewards[+1], rewards[-1] of the FINAL position, as sgx_playout reports them */
+    uint8_t *done_dev, *ending_invalid_dev;   /* [N] out, nullable */
+    int8_t  *player_dev;           /* [N] out, nullable: the mover at the final position */
+    uint8_t *invalid_action_dev;   /* [N] out, nullable: 1 = the agent's action was refused as sgx_step refuses it; position unchanged, the bot did not move */
+    uint8_t *moved_dev;            /* [N] out, nullable: SGX_VS_MOVED_* */
+    int32_t *reply_action_dev;     /* [N] out, nullable: the bot's move, flat spatial index in the BOT's perspective (what sgx_replay takes); -1 = none */
+    int32_t  agent;                /* +1 / -1, read when agent_dev is NULL */
+    int32_t  flags;                /* SGX_VS_SEE_ALL */
+} sgx_vs_io;                       /* 9 pointers + 2 int32 = 80 bytes */
+int sgx_step_vs(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_vs_io *io,
+                const uint16_t *weights /* HOST memory, [4][13][14], entries <= SGX_PLAYOUT_WEIGHT_MAX */, uint64_t draw, void *stream);
 
 /* Replay: every slot of `dst` becomes a position of `src` advanced by a GIVEN list of actions, all entries in ONE launch -- what a learner
  * that kept start records and the action log of sgx_step_traj does to get back to (game, t), what a search does to re-derive a node from

@@ -23,6 +23,8 @@ POOL_RANDOM_FIRST_PLAYER, POOL_RESTART_CLOCK = 1, 2
 LAUNCH_WAVE, LAUNCH_LANE, LAUNCH_MULTI_STEP, LAUNCH_MULTI_STEP_WAVE, LAUNCH_PLAYOUT, LAUNCH_REPLAY, LAUNCH_CHILDREN = 0, 1, 2, 3, 4, 5, 6
 LAUNCH_REPLAY_TRACKED = 8
 LAUNCH_PLAYOUT_WEIGHTED = 7
+LAUNCH_STEP_VS = 9
+VS_SEE_ALL, VS_MOVED_AGENT, VS_MOVED_BOT = 1, 1, 2
 PLAYOUT_SEE_ALL = 1
 PLAYOUT_WEIGHTS_SHAPE, PLAYOUT_WEIGHT_MAX = (4, 13, 14), 4095
 BELIEF_WEIGHT_MAX = 4095                 # beliefs of sgx_determinize_weighted: uint16 [2, 12, cells] per table
@@ -37,7 +39,7 @@ EXPORTED_SYMBOLS = (
     'sgx_abi_version', 'sgx_build_id', 'sgx_supports_geometry', 'sgx_last_error', 'sgx_num_envs', 'sgx_record_bytes', 'sgx_spatial_channels', 'sgx_num_spatial_actions',
     'sgx_action_size_1d', 'sgx_build_obs_lut', 'sgx_build_full_obs_lut', 'sgx_build_original_obs_lut', 'sgx_create', 'sgx_destroy', 'sgx_set_nt_stores', 'sgx_set_lane_kernel', 'sgx_set_half_wave', 'sgx_set_steps_barrier', 'sgx_set_multi_step', 'sgx_last_launch_kind', 'sgx_set_xcd_skew', 'sgx_set_xcd_shares', 'sgx_get_xcd_shares', 'sgx_set_setup_table', 'sgx_set_start_pool', 'sgx_set_start_index_out', 'sgx_start_pool_size', 'sgx_reset',
     'sgx_observe', 'sgx_time_observe', 'sgx_mem_probe', 'sgx_store_probe', 'sgx_alloc_outputs', 'sgx_set_placement_target', 'sgx_free_outputs', 'sgx_step', 'sgx_host_alloc', 'sgx_host_free', 'sgx_step_sync', 'sgx_step_n', 'sgx_step_ring', 'sgx_step_traj', 'sgx_rollout', 'sgx_compact_obs_stride', 'sgx_compact_mask_words', 'sgx_decode_obs', 'sgx_decode_mask', 'sgx_sample_valid', 'sgx_choose_actions', 'sgx_export_state', 'sgx_import_state', 'sgx_import_state_checked', 'sgx_step_states', 'sgx_set_general_states', 'sgx_copy_envs', 'sgx_expand', 'sgx_determinize', 'sgx_determinize_weighted', 'sgx_playout', 'sgx_playout_weighted', 'sgx_replay', 'sgx_count_moves', 'sgx_expand_all', 'sgx_state_keys', 'sgx_get_env_info',
-    'sgx_set_leaf_values', 'sgx_leaf_values_set', 'sgx_set_replay_origins', 'sgx_replay_origins_set',
+    'sgx_set_leaf_values', 'sgx_leaf_values_set', 'sgx_set_replay_origins', 'sgx_replay_origins_set', 'sgx_step_vs',
 )
 
 
@@ -61,6 +63,12 @@ class SgxTrajIO(C.Structure):
 class SgxPlayoutIO(C.Structure):
     _fields_ = [('reward_dev', C.c_void_p), ('done_dev', C.c_void_p), ('ending_invalid_dev', C.c_void_p), ('player_dev', C.c_void_p),
                 ('length_dev', C.c_void_p), ('max_steps', C.c_int32), ('flags', C.c_int32)]
+
+
+class SgxVsIO(C.Structure):
+    _fields_ = [('actions_dev', C.c_void_p), ('agent_dev', C.c_void_p), ('reward_dev', C.c_void_p), ('done_dev', C.c_void_p),
+                ('ending_invalid_dev', C.c_void_p), ('player_dev', C.c_void_p), ('invalid_action_dev', C.c_void_p), ('moved_dev', C.c_void_p),
+                ('reply_action_dev', C.c_void_p), ('agent', C.c_int32), ('flags', C.c_int32)]
 
 
 class SgxReplayIO(C.Structure):
@@ -221,6 +229,8 @@ def _bind(L):
     L.sgx_playout.argtypes = [vp, vp, vp, C.POINTER(SgxPlayoutIO), u64, vp]
     L.sgx_playout_weighted.restype = C.c_int
     L.sgx_playout_weighted.argtypes = [vp, vp, vp, C.POINTER(SgxPlayoutIO), C.POINTER(C.c_uint16), C.c_int32, u64, vp]
+    L.sgx_step_vs.restype = C.c_int
+    L.sgx_step_vs.argtypes = [vp, vp, vp, C.POINTER(SgxVsIO), C.POINTER(C.c_uint16), u64, vp]
     L.sgx_replay.restype = C.c_int
     L.sgx_replay.argtypes = [vp, vp, vp, C.POINTER(SgxReplayIO), vp]
     L.sgx_count_moves.restype = C.c_int

@@ -296,7 +296,7 @@ __host__ __device__ inline uint64_t sgx_rng(uint64_t seed, uint64_t g, uint64_t 
 }
 __host__ __device__ inline uint32_t rng_below(uint64_t r, uint32_t n) { return (uint32_t)(((r >> 32) * (uint64_t)n) >> 32); }
 enum { STREAM_SETUP = 0, STREAM_ACTION = 1, STREAM_SHUFFLE_P1 = 2, STREAM_SHUFFLE_P2 = 3, STREAM_POOL = 4, STREAM_DETERMINIZE = 5, STREAM_PLAYOUT = 6,
-       STREAM_DETERMINIZE_WEIGHTED = 7 };
+       STREAM_DETERMINIZE_WEIGHTED = 7, STREAM_REPLY = 8 };
 // A game that starts from a start pool (sgx_set_start_pool): game `j` of env `g` takes record pool_index() and, with
 // SGX_POOL_RANDOM_FIRST_PLAYER, the first mover pool_first_player() says (0: the record's own).  A stream of its own: no other draw moves.
 __host__ __device__ inline int pool_index(uint64_t seed, uint64_t g, uint64_t j, int n_pool) {

@@ -84,6 +84,7 @@ const char g_build_id[] = "SGX_BUILD_ID=" SGX_BUILD_ID;
 #include "sgx_step.h"
 #include "sgx_pool_frame.h"
 #include "sgx_playout.h"
+#include "sgx_step_vs.h"
 #include "sgx_replay.h"
 #include "sgx_children.h"
 #include "sgx_keys.h"
@@ -2370,6 +2371,37 @@ SGX_API int sgx_playout_weighted(sgx_env *dst, sgx_env *src, const int32_t *src_
     memcpy(sp.weights, weights, sizeof(sp.weights));       // the table leaves with the launch's arguments: the caller's copy is free again
     if (int rc = launch_leaf_or_plain<WeightedPlayoutK>(dst, sp, stream)) return rc;
     dst->last_kind = SGX_LAUNCH_PLAYOUT_WEIGHTED;
+    return SGX_OK;
+}
+
+namespace {
+struct StepVsK { template <int R, int C, int VAR> static auto kernel() { return &step_vs_kernel<R, C, VAR>; } };
+}  // namespace
+
+SGX_API int sgx_step_vs(sgx_env *dst, sgx_env *src, const int32_t *src_index_dev, const sgx_vs_io *io, const uint16_t *weights, uint64_t draw, void *stream) {
+    // the policy first, as in sgx_playout_weighted: what can be said about it needs no handle
+    if (!weights) return fail(SGX_EINVAL, "sgx_step_vs: weights is NULL%s");
+    for (int i = 0; i < WT_ENTRIES; ++i)
+        if (weights[i] > SGX_PLAYOUT_WEIGHT_MAX)
+            return fail(SGX_EINVAL, "%s", ("sgx_step_vs: weights[" + std::to_string(i / (WT_TYPES * WT_TARGETS)) + "][" + std::to_string(i / WT_TARGETS % WT_TYPES) + "][" +
+                                           std::to_string(i % WT_TARGETS) + "] = " + std::to_string((int)weights[i]) + " exceeds " + std::to_string(SGX_PLAYOUT_WEIGHT_MAX)).c_str());
+    if (!dst || !src || !io) return fail(SGX_EINVAL, "sgx_step_vs: handle or io is NULL%s");
+    if (io->flags & ~SGX_VS_SEE_ALL) return fail(SGX_EINVAL, "sgx_step_vs: unknown flags bits%s");
+    if (!io->agent_dev && io->agent != 1 && io->agent != -1) return fail(SGX_EINVAL, "sgx_step_vs: agent must be +1 or -1 when agent_dev is NULL%s");
+    if (int rc = check_root_source("sgx_step_vs", dst, src, src_index_dev, dst->n_envs, "dst")) return rc;
+    // (a dst with a start pool is accepted: the call never restarts a game and writes no start index, restarts are the caller's sgx_reset)
+    if (int rc = check_aligned("sgx_step_vs", "src_index_dev", src_index_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_step_vs", "actions_dev", io->actions_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_step_vs", "reward_dev", io->reward_dev, 4)) return rc;
+    if (int rc = check_aligned("sgx_step_vs", "reply_action_dev", io->reply_action_dev, 4)) return rc;
+    SGX_ON_DEVICE(dst->device);
+    StepVsParams sp{pool_params(dst, src, src_index_dev, 0), PlayParams{draw, result_out(*io), nullptr, 0},
+                    VsArgs{io->actions_dev, io->agent_dev, io->invalid_action_dev, io->moved_dev, io->reply_action_dev, io->agent_dev ? 1 : io->agent,
+                           (io->flags & SGX_VS_SEE_ALL) ? 1 : 0},
+                    {}};
+    memcpy(sp.weights, weights, sizeof(sp.weights));       // the table leaves with the launch's arguments: the caller's copy is free again
+    if (int rc = launch_pool_kernel<StepVsK>(dst, sp, stream)) return rc;
+    dst->last_kind = SGX_LAUNCH_STEP_VS;
     return SGX_OK;
 }
 

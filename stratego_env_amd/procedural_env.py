@@ -583,6 +583,25 @@ class PlayoutResult:
         return torch.where(p > 0, self.reward[:, 0], self.reward[:, 1])
 
 
+class StepVsResult:
+    """What step_vs reports per slot (device tensors), of the position the call reached: reward float32 [n,2], done uint8, ending_invalid
+    uint8, player int8 (its mover) as for a playout; invalid_action uint8 (1 = the agent's action was refused: position unchanged, the bot
+    stayed still), moved uint8 (bit 0: the agent moved, bit 1: the bot), reply_action int32 (the bot's move as a flat spatial index in
+    the BOT's perspective -- what replay takes --, -1 = none)."""
+
+    def __init__(self, reward, done, ending_invalid, player, invalid_action, moved, reply_action):
+        self.reward, self.done, self.ending_invalid, self.player = reward, done, ending_invalid, player
+        self.invalid_action, self.moved, self.reply_action = invalid_action, moved, reply_action
+
+    @classmethod
+    def empty(cls, n, device):
+        u8 = lambda: torch.empty((n,), dtype=torch.uint8, device=device)
+        return cls(torch.empty((n, 2), dtype=torch.float32, device=device), u8(), u8(), torch.empty((n,), dtype=torch.int8, device=device),
+                   u8(), u8(), torch.empty((n,), dtype=torch.int32, device=device))
+
+    value_for = PlayoutResult.value_for
+
+
 class ReplayResult:
     """What replay reports per slot (device tensors): applied int32 (moves applied), consumed int32 (entries gone past, applied or
     skipped), stop uint8 (0 = the list was exhausted, 1 = the game was over, 2 = an invalid action: entry `consumed` is the offending one),
@@ -774,6 +793,15 @@ class PackedStates:
                                                        int(draw) & 0xFFFFFFFFFFFFFFFF, vec._stream()), vec._L)
         vec._next_actions_fresh = False
         return res
+
+    def step_vs(self, src, actions, agent, weights, see_all=False, draw=0, src_index=None):
+        """self[i] = src[src_index[i]] after the agent's move actions[i] and the reply of the table bot `weights`, both in one launch
+        (sgx_step_vs; the rule is in include/stratego_mi355x.h); `src` stays what it was.  `src`: a PackedStates (this pool itself for an
+        in-place call without src_index) or a live VecStrategoEnv of the same variant.  actions: int32 [n] flat spatial indices in the
+        mover's perspective, or None (the bot opens where it is to move); agent: +1 / -1 or an int8 tensor [n]; weights, see_all: as
+        playout takes them, for the bot; draw: the key of the replies.  -> StepVsResult.  (VecStrategoEnv.step_vs is the same call
+        with a live env as the destination.)"""
+        return self._vec.step_vs(actions, agent, weights, see_all=see_all, draw=draw, src=src, src_index=src_index)
 
     def replay(self, src, actions, lengths=None, src_index=None, skip_invalid=False, actions_1d=False, allow_piece_oscillation=False,
                track_origins=False, origins_in=None):

@@ -278,11 +278,12 @@ class VecStrategoEnv:
         _lib.check(self._L.sgx_set_xcd_shares(self._h, arr), self._L)
 
     # ---- API -----------------------------------------------------------------------------------------
-    def reset(self, p1_maps=None, p2_maps=None, env_select=None):
+    def reset(self, p1_maps=None, p2_maps=None, env_select=None, observe=True):
         """Start new games (all envs, or those with env_select[i] != 0) and return (obs, mask, player).
 
         p1_maps / p2_maps: int8 [N, R, C] own-side piece maps (create_initial_state inputs, penv:38-60);
-        omit both to sample setups on the device."""
+        omit both to sample setups on the device.  observe=False: the records only, nothing is rendered and None is returned (a caller
+        that moves on before it looks: vs_env.VsBotVecEnv lets the bot open first)."""
         sel = None
         if env_select is not None:
             sel = env_select.to(device=self.device, dtype=torch.uint8).contiguous()
@@ -306,7 +307,7 @@ class VecStrategoEnv:
                     self.placement_report = self.tune_placement(max_extra_bytes=min(8 << 30, free // 4))
                 except RuntimeError as e:          # (no memory for candidates next to another tenant: the plain tensors stay)
                     self.placement_report = {'failed': str(e)}
-        return self.observe()
+        return self.observe() if observe else None
 
     # ---- start pools: games that start from given positions (maenv:519-527, util.py:374-387 for a batch) -------------------------
     @property
@@ -878,6 +879,56 @@ class VecStrategoEnv:
                     _lib.check(self._L.sgx_replay(self._h, src_vec._h, _ptr(si), C.byref(io), self._stream()), self._L)
             finally:                                                 # the setting lasts for this call alone, also when it raises
                 self._L.sgx_set_replay_origins(self._h, None, None)
+        self._next_actions_fresh = False
+        return res
+
+    def step_vs(self, actions, agent, weights, see_all=False, draw=0, src=None, src_index=None, out=None):
+        """The agent's move and a table bot's reply for every game, in ONE launch that writes no observation (sgx_step_vs; the rule is in
+        include/stratego_mi355x.h).  Where the game is not over and the agent is to move, actions[i] is applied as step() applies it (a
+        refused action leaves the position alone: invalid_action = 1, the bot stays still); where the bot is to move then -- or from the
+        start, the agent not being the mover -- it moves once, drawn from `weights` as a weighted playout draws its moves.  There is no
+        auto-reset and a finished game is left as it is, so afterwards every game that is neither over nor refused has the agent to move;
+        observe() renders it.
+        actions: int32 [N] flat (R,C,K) indices in the mover's perspective, or None: no agent moves, the bot opens where it is to move.
+        agent: +1 / -1, or an int8 tensor [N] of the agent's side per game (< 0: -1).  weights: [4, 13, 14] integers in [0, 4095]
+        (stratego_env_amd.playout_policies), read before the call returns; see_all=True lets the bot see the agent's true piece types,
+        the default is what its partial observation shows.  draw: the replies are keyed by (seed, env id, draw, turn): pass another
+        one with every call.  src / src_index: the positions come from src[src_index[i]] (a PackedStates, a snapshot or another env)
+        instead of this env's own.  out: a StepVsResult to fill instead of a new one.
+        -> StepVsResult: reward [N,2], done, ending_invalid, player (of the position reached), invalid_action, moved (bit 0: the agent,
+        bit 1: the bot), reply_action (the bot's move in the bot's perspective, -1 = none)."""
+        from .procedural_env import StepVsResult, playout_weights
+        n, dev = self.num_envs, self.device
+        table = playout_weights(weights)
+        src_vec = self if src is None else getattr(src, '_vec', src)
+        if src_vec is self and src_index is not None:
+            raise ValueError("an in-place step_vs through src_index would race (a record may be overwritten before it is read): "
+                             "step into another pool")
+        a = None
+        if actions is not None:
+            a = actions
+            if not isinstance(a, torch.Tensor) or a.dtype != torch.int32 or a.device != dev or not a.is_contiguous():
+                a = torch.as_tensor(a).to(device=dev, dtype=torch.int32).contiguous()
+            if a.numel() != n:
+                raise ValueError("actions must hold one int32 per game (%d)" % n)
+        side, sides = 1, None
+        if isinstance(agent, (int, np.integer)):
+            if int(agent) not in (1, -1):
+                raise ValueError("agent must be +1, -1 or an int8 tensor [N]")
+            side = int(agent)
+        else:
+            sides = agent
+            if not isinstance(sides, torch.Tensor) or sides.dtype != torch.int8 or sides.device != dev or not sides.is_contiguous():
+                sides = torch.as_tensor(sides).to(device=dev, dtype=torch.int8).contiguous()
+            if sides.numel() != n:
+                raise ValueError("agent must be +1, -1 or an int8 tensor [N]")
+        si = None if src_index is None else torch.as_tensor(src_index).to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+        res = out if out is not None else StepVsResult.empty(n, dev)
+        io = _lib.SgxVsIO(_ptr(a), _ptr(sides), res.reward.data_ptr(), res.done.data_ptr(), res.ending_invalid.data_ptr(), res.player.data_ptr(),
+                          res.invalid_action.data_ptr(), res.moved.data_ptr(), res.reply_action.data_ptr(), side, _lib.VS_SEE_ALL if see_all else 0)
+        with torch.cuda.device(dev):
+            _lib.check(self._L.sgx_step_vs(self._h, src_vec._h, _ptr(si), C.byref(io), table.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                           int(draw) & 0xFFFFFFFFFFFFFFFF, self._stream()), self._L)
         self._next_actions_fresh = False
         return res
 

@@ -2,6 +2,8 @@
 
     python tools/kernel_notes.py <lib.so> [substring of the mangled kernel name]
     python tools/kernel_notes.py <parent.so> --against <branch.so>     both side by side; exit status 1 if a kernel of the parent got worse
+    python tools/kernel_notes.py <parent.so> --identical <branch.so>   the exact comparison, with sgpr and code size; exit status 1 if a kernel
+                                                                       of the parent differs in any figure or a new kernel uses scratch
 
 The rule of --against: for every kernel name of the parent, vgpr, scratch and LDS of the branch are <= the parent's (a missing kernel is worse)."""
 import os
@@ -53,9 +55,45 @@ def compare(parent_so, branch_so):
     return len(worse)
 
 
+def kernel_notes_with_size(so):
+    """kernel name -> (vgpr, sgpr, LDS bytes, scratch bytes, code bytes): the notes, and the size of the kernel's symbol in the code object"""
+    with tempfile.TemporaryDirectory() as td:
+        import shutil
+        shutil.copy(so, os.path.join(td, 'lib.so'))
+        subprocess.check_call([os.path.join(LLVM, 'llvm-objdump'), '--offloading', os.path.join(td, 'lib.so')], stdout=subprocess.DEVNULL, cwd=td)
+        co = os.path.join(td, [f for f in os.listdir(td) if 'gfx950' in f][0])
+        syms = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--symbols', '--wide', co], capture_output=True, text=True, check=True).stdout
+    size = {}
+    for line in syms.splitlines():
+        p = line.split()
+        if len(p) >= 8 and p[3] == 'FUNC':
+            size[p[7]] = int(p[2], 0)
+    return {k: (r['vgpr'], r['sgpr'], r['lds'], r['scratch'], size.get(k, -1)) for k, r in kernel_notes(so).items()}
+
+
+def compare_identical(parent_so, branch_so):
+    """The exact comparison (the format of profiles/step_vs_kernel_notes.txt): every kernel of the parent has identical figures in the
+    branch, and no new kernel uses scratch.  Returns the number of kernels that break the rule."""
+    a, b = kernel_notes_with_size(parent_so), kernel_notes_with_size(branch_so)
+    diff = [k for k in a if a[k] != b.get(k)]
+    new = sorted(set(b) - set(a))
+    print("kernel resources from the metadata of the gfx950 code object (llvm-readelf --notes; code size: the kernel symbol's size, llvm-readelf --symbols)")
+    print("of the main library, parent commit | this commit: vgpr / sgpr / LDS bytes / scratch bytes / code bytes")
+    print("rule: every kernel symbol of the parent is in this commit's code object with IDENTICAL figures; \"new\" = a kernel the parent does not have, and it uses no scratch")
+    print("%d kernels in the parent, %d here; kernels of the parent whose figures differ: %d; new kernels: %d, of them with scratch: %d\n"
+          % (len(a), len(b), len(diff), len(new), sum(1 for k in new if b[k][3])))
+    fmt = lambda r: '%3d %3d %6d %5d %6d' % r if r else '  -   -      -     -      -'
+    for k in sorted(a) + new:
+        mark = '  DIFFERS' if k in diff else '' if k in a else '  new'
+        print("%-56.56s %s | %s%s" % (short_name(k), fmt(a.get(k)), fmt(b.get(k)), mark))
+    return len(diff) + sum(1 for k in new if b[k][3])
+
+
 if __name__ == '__main__':
     if len(sys.argv) == 4 and sys.argv[2] == '--against':
         sys.exit(1 if compare(sys.argv[1], sys.argv[3]) else 0)
+    if len(sys.argv) == 4 and sys.argv[2] == '--identical':
+        sys.exit(1 if compare_identical(sys.argv[1], sys.argv[3]) else 0)
     pat = sys.argv[2] if len(sys.argv) > 2 else ''
     for name, r in sorted(kernel_notes(sys.argv[1]).items()):
         if pat in name:

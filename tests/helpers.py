@@ -9,6 +9,7 @@ from oracle import oracle as orc
 from stratego_env_amd.config import VARIANTS
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+MASK, POBS, FOBS = 'valid_actions_mask', 'partial_observation', 'full_observation'       # the keys of an observation dict
 
 
 def load_variants_json():

@@ -11,6 +11,7 @@ from stratego_env_amd import _lib
 from stratego_env_amd import build as hip_build
 from stratego_env_amd.config import VARIANTS
 from tests.helpers import load_variants_json
+from tests.step_checks import _kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -164,27 +165,6 @@ def test_product_package_never_imports_oracle():
                 assert not re.search(r'^\s*(from|import)\s+oracle\b', src, re.M), f
                 # (the device sources may NAME the oracle file in a comment -- the RNG is restated there -- nothing else may)
                 assert 'stratego_oracle' not in src or os.path.basename(dp) == 'csrc', f
-
-
-def _kernel_resources(tmp_path):
-    """{mangled kernel name: {vgpr, sgpr, scratch, lds}} read from the gfx950 code object inside the SHIPPED library (the notes of the
-    offload bundle: what the GPU box will run, and seconds instead of the minutes of a fresh hipcc -S)."""
-    import shutil
-    import subprocess
-    llvm = '/opt/rocm/lib/llvm/bin'
-    so = tmp_path / 'lib.so'
-    hip_build.build()                                  # (a no-op when the library matches the sources: its build id is their hash)
-    shutil.copy(hip_build.LIB_PATH, so)
-    subprocess.check_call([os.path.join(llvm, 'llvm-objdump'), '--offloading', str(so)], stdout=subprocess.DEVNULL, cwd=str(tmp_path))
-    cos = [f for f in os.listdir(tmp_path) if 'gfx950' in f]
-    assert len(cos) == 1, cos
-    notes = subprocess.run([os.path.join(llvm, 'llvm-readelf'), '--notes', str(tmp_path / cos[0])], capture_output=True, text=True, check=True).stdout
-    res = {}
-    for blk in re.split(r'\n\s+- \.agpr_count:', notes)[1:]:
-        g = lambda k: int(re.search(r'\.%s:\s+(\d+)' % k, blk).group(1))
-        res[re.search(r'\.name:\s+(\S+)', blk).group(1)] = dict(vgpr=g('vgpr_count'), sgpr=g('sgpr_count'), scratch=g('private_segment_fixed_size'),
-                                                                 lds=g('group_segment_fixed_size'))
-    return res
 
 
 def test_hot_kernels_use_no_scratch_memory(tmp_path):

@@ -130,7 +130,7 @@ def test_the_library_exports_the_entry_points():
 def test_the_new_kernels_use_no_scratch_memory(tmp_path):
     """count_kernel and children_kernel on every board of the reference, in every games-per-wave variant the library holds, and the three scan
     kernels: no scratch memory (read from the shipped library)."""
-    from tests.test_cabi_cpu import _kernel_resources
+    from tests.step_checks import _kernel_resources
     res = _kernel_resources(tmp_path)
     boards = {(10, 10), (15, 15), (8, 8), (6, 6), (5, 5), (4, 4), (3, 4)}
     for kernel in ('12count_kernel', '15children_kernel'):

@@ -11,31 +11,11 @@ from stratego_env_amd import _lib
 from stratego_env_amd import build as hip_build
 from stratego_env_amd.config import VARIANTS
 from tests import determinize_rule as dr
-from tests.helpers import _blank_state, _put, load_games, oracle_env
+from tests.helpers import _blank_state, _put
+from tests.pool_roots import fives_position, sampled_states
 
 GAME_SETS = ['barrage', 'standard', 'octa_barrage', 'fives', 'micro']
 DRAWS = (0, 1, 1 << 40)
-
-
-def sampled_states(name, n_games=3, every=5):
-    """(state, mover) pairs along the first golden games of a variant: the start and every `every`-th position."""
-    g = load_games(name)
-    off = g['offsets']
-    env = oracle_env(name)
-    out = []
-    for gi in range(min(n_games, len(off) - 1)):
-        env.reset(g['p1_maps'][gi].astype(np.int64), g['p2_maps'][gi].astype(np.int64))
-        out.append((env.state.copy(), env.player))
-        for n, k in enumerate(range(off[gi], off[gi + 1])):
-            if g['errors'][k]:
-                continue
-            _, _, done, _ = env.step({env.player: int(g['actions'][k])})
-            if done['__all__']:
-                out.append((env.state.copy(), env.player))          # (no special case for finished games)
-                break
-            if n % every == 0:
-                out.append((env.state.copy(), env.player))
-    return out
 
 
 @pytest.mark.parametrize('name', GAME_SETS)
@@ -100,17 +80,6 @@ def test_inconsistent_states_are_returned_unchanged():
             st[3 + (0 if opp == 1 else 1), 2, 2] = bad_type
             out, hidden = dr.determinize(st, observer, observer, 0, 0, 0)
             assert hidden == 3
-
-
-def fives_position():
-    """Fives, observer +1: the opponent's five pieces {4, 5, 6, 7, flag} all hidden, four never moved and one moved: 4 * 4! = 96 worlds."""
-    st = _blank_state(5, 5, VARIANTS['fives'].max_turns, 6)
-    for c, t in enumerate((4, 11, 6, 7)):
-        _put(st, -1, 0, c, t)
-    _put(st, -1, 1, 4, 5, moved=True)
-    for c, t in enumerate((4, 5, 6, 7, 11)):
-        _put(st, 1, 4, c, t)
-    return st, 96
 
 
 def barrage_like_position():

@@ -1,8 +1,6 @@
 """Belief-weighted determinization (sgx_determinize_weighted) without a GPU: the binding, the numpy restatement of the rule
 (tests/determinize_weighted_rule.py, what the device kernel is held to bit for bit in tests/test_gpu_determinize_weighted.py) against the
 oracle's rules and the consequences the header promises, its exact distribution, and the tables of stratego_env_amd.beliefs."""
-import collections
-import functools
 import os
 import re
 
@@ -14,47 +12,12 @@ from stratego_env_amd import _lib, beliefs as bl, setups as S
 from stratego_env_amd.config import VARIANTS
 from tests import determinize_weighted_rule as wr
 from tests.helpers import _blank_state, _put
-from tests.test_determinize_cpu import fives_position, sampled_states
+from tests.pool_roots import fives_position, sampled_states
+from tests.tables import chi2_against, fives_samples, one_hot_truth, skewed_fives_table, third_zero_belief
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAME_SETS = ['barrage', 'standard', 'standard2', 'octa_barrage', 'medium', 'fives', 'tiny', 'micro']      # every board size
 DRAWS = (0, 1, 1 << 40)
-N_DRAWS = 65536
-
-
-def third_zero_table(cells, seed=0, shape=None):
-    """A seeded random table, values to 4095, a third of the entries 0 (the GPU test uses the same)."""
-    rs = np.random.RandomState(seed)
-    shape = (2, 12, cells) if shape is None else shape
-    w = rs.randint(1, 4096, size=shape)
-    w[rs.random_sample(shape) < 1.0 / 3.0] = 0
-    return w.astype(np.uint16)
-
-
-def one_hot_truth(state):
-    """Weight 1 exactly where a piece of that type stands, for both players."""
-    cells = state.shape[1] * state.shape[2]
-    w = np.zeros((2, 12, cells), dtype=np.uint16)
-    for p in range(2):
-        flat = state[p].reshape(-1)
-        for c in np.flatnonzero(flat):
-            w[p, flat[c] - 1, c] = 1
-    return w
-
-
-def skewed_fives_table():
-    """The table of the distribution test on fives_position() (hidden cells 0, 1, 2, 3 never moved and 9 moved; types 4, 5, 6, 7, flag):
-    uneven weights with zeros on the hidden cells -- the flag never on cell 1 where it truly stands, the 6 never on cell 1, the 5 never on
-    cell 3 -- chosen on the CPU so that the worlds of expected count below 5 hold less than 5 % of the mass; elsewhere a seeded third-zero
-    filling that the position never reads."""
-    w = third_zero_table(25, seed=3).astype(np.int64)
-    hid = [0, 1, 2, 3, 9]
-    w[1][11 - 1][hid] = [800, 0, 300, 1, 4095]          # (cell 9 has moved: the flag's weight there is never read; cell 3: the rare worlds)
-    w[1][7 - 1][hid] = [1, 2, 3, 4, 5]
-    w[1][6 - 1][hid] = [5, 0, 1, 2, 2]
-    w[1][5 - 1][hid] = [1, 1, 1, 0, 3]
-    w[1][4 - 1][hid] = [0, 0, 0, 0, 0]                  # the last instance dealt: one cell is left, whatever it weighs (off_belief counts it)
-    return w.astype(np.uint16)
 
 
 def test_the_binding():
@@ -82,7 +45,7 @@ def test_the_rule_against_the_oracle(name):
     ru = orc.OracleRules(v.rows, v.columns)
     states = sampled_states(name, n_games=2, every=7)
     assert len(states) >= 4
-    table = third_zero_table(cells, seed=11)
+    table = third_zero_belief(cells, seed=11)
     changed = fell_back = 0
     for si, (st, mover) in enumerate(states):
         truth = one_hot_truth(st)
@@ -148,7 +111,7 @@ def test_a_flag_or_bomb_on_a_moved_hidden_cell_is_refused():
             _put(st, opp, 0, 3, 11 if bad_type == 12 else 6)
             _put(st, observer, 4, 0, 11)
             _put(st, observer, 4, 1, 7, moved=True)
-            out, hidden, off = wr.determinize_weighted(st, observer, observer, third_zero_table(25), 0, 0, 5)
+            out, hidden, off = wr.determinize_weighted(st, observer, observer, third_zero_belief(25), 0, 0, 5)
             assert hidden == -1 and off == 0 and np.array_equal(out, st)
 
 
@@ -156,7 +119,7 @@ def test_the_batch_form_indexes_tables_by_source_record():
     states = sampled_states('fives', n_games=1, every=3)[:4]
     st = np.stack([s for s, _ in states])
     movers = np.asarray([m for _, m in states])
-    tables = third_zero_table(25, seed=2, shape=(4, 2, 12, 25))
+    tables = third_zero_belief(25, seed=2, shape=(4, 2, 12, 25))
     idx = np.asarray([3, 0, 3, 1, 2, 2])
     out, hidden, off = wr.determinize_weighted_batch(st, movers, 0, tables, 5, 100, 2, idx)
     for i, s in enumerate(idx):
@@ -167,40 +130,6 @@ def test_the_batch_form_indexes_tables_by_source_record():
 
 
 # ---- the distribution ------------------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def fives_samples(kind):
-    """65,536 worlds of fives_position() for slots 0 .. 65,535 of seed 0, draw 0, with the constant table ('constant': every entry 7) or
-    skewed_fives_table() ('skewed') -> (layers int64 [N, 25], off_belief int32 [N]).  Read-only: shared by the tests."""
-    st, _ = fives_position()
-    table = np.full((2, 12, 25), 7, dtype=np.uint16) if kind == 'constant' else skewed_fives_table()
-    layers, off = wr.sample_layers(st, 1, 1, table, 0, np.arange(N_DRAWS), 0)
-    layers.setflags(write=False)
-    off.setflags(write=False)
-    return layers, off
-
-
-def chi2_against(layers, probs):
-    """Pearson's chi-squared of the sampled worlds against the exact probabilities {layer bytes: Fraction}: every world of expected count
-    >= 5 a cell of its own, the others pooled into one.  -> (statistic, degrees of freedom, pooled mass, worlds seen that have
-    probability 0)."""
-    counts = collections.Counter(row.tobytes() for row in layers)
-    n = len(layers)
-    impossible = sum(c for k, c in counts.items() if probs.get(k, 0) == 0)
-    stat, cells_used, pooled_p, pooled_c = 0.0, 0, 0.0, 0
-    for k, p in probs.items():
-        e = float(p) * n
-        if e >= 5.0:
-            stat += (counts.get(k, 0) - e) ** 2 / e
-            cells_used += 1
-        else:
-            pooled_p += float(p)
-            pooled_c += counts.get(k, 0)
-    if pooled_p > 0:
-        stat += (pooled_c - pooled_p * n) ** 2 / (pooled_p * n)
-        cells_used += 1
-    return stat, cells_used - 1, pooled_p, impossible
-
-
 def test_the_vectorised_sampler_is_the_rule():
     st, _ = fives_position()
     for kind in ('constant', 'skewed'):

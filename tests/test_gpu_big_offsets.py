@@ -202,7 +202,7 @@ def _norm(written, steps):
 def _run_against_witnesses(name, n, seq, row_bytes, chunk, front=bo.FRONT_4G, every=1, final_check=None, **handle_kw):
     """The whole procedure of a stepping case; row_bytes: of the tensor whose boundaries name the straddling games."""
     import torch
-    from tests.test_gpu_guard_bands import Oracle
+    from tests.guard_bands import Oracle
     dev = torch.device('cuda', 0)
     anchors = bo.straddlers(n, row_bytes)
     compact = bool(handle_kw.get('compact_outputs'))
@@ -498,7 +498,7 @@ def test_decoders_past_2_31_floats():
     the oracle at the anchors."""
     import torch
     from stratego_env_amd.vec_env import VecStrategoEnv
-    from tests.test_gpu_guard_bands import Oracle
+    from tests.guard_bands import Oracle
     name, chunk = 'standard2', 16384
     dev = torch.device('cuda', 0)
     n = bo.thresholds(_obs_bytes(name), 4).e31 + 100
@@ -596,7 +596,7 @@ def test_chooser_past_4_gib_of_logits():
             bo.assert_rows_equal(got[c].t, out, k, (c, where))
         w.close()
     # anchors: the chosen action is valid in the oracle's mask of that game, and the sampler's is the oracle's draw
-    from tests.test_gpu_guard_bands import Oracle
+    from tests.guard_bands import Oracle
     for g in bo.straddlers(n, na * 4):
         ora = Oracle(name, SEED, g, 1, auto_reset=True)
         cur = ora.current()

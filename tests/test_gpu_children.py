@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from tests import children_rule as cr
-from tests.test_gpu_playout import CASES, GAMES_PER_WORKGROUP, N_SRC, _np, _pool_from, _roots
+from tests.pool_roots import CASES, GAMES_PER_WORKGROUP, N_SRC, _np, _pool_from, _roots
 
 pytestmark = pytest.mark.gpu
 
@@ -222,7 +222,7 @@ def test_null_outputs_and_guard_bands():
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena
+    from tests.guard_bands import Arena, pool_arenas
     name = 'fives'
     env, states, players, per_root = _setup(name)
     ch = cr.Children(name, states, players, None, per_root)
@@ -233,7 +233,6 @@ def test_null_outputs_and_guard_bands():
     filler = int(np.flatnonzero(ch.counts == 0)[0])
     vec = pool._vec
     L = vec._L
-    dtypes = {'float32': torch.float32, 'uint8': torch.uint8, 'int8': torch.int8, 'int32': torch.int32}
     counts_a = Arena('counts', (N_SRC,), torch.int32, 4, vec.device)
     offsets_a = Arena('offsets', (N_SRC + 1,), torch.int64, 16, vec.device)
     assert L.sgx_count_moves(env._h, None, N_SRC, counts_a.t.data_ptr(), offsets_a.t.data_ptr(), vec._stream()) == 0, L.sgx_last_error()
@@ -248,8 +247,7 @@ def test_null_outputs_and_guard_bands():
     assert offsets_a.host().tobytes() == ch.offsets.tobytes()
 
     def arenas(byte_phase, word_phase):
-        return {k: Arena(k, (n, w) if w > 1 else (n,), dtypes[t], word_phase if t in ('float32', 'int32') else byte_phase, vec.device)
-                for k, w, t in OUT_SPECS}
+        return pool_arenas(OUT_SPECS, n, vec.device, byte_phase, word_phase)
 
     def call(ptrs):
         pool.copy_from(env, src_index=torch.full((n + extra,), filler, dtype=torch.int32, device='cuda'))
@@ -382,7 +380,7 @@ def test_a_generic_geometry():
     import torch
     from stratego_env_amd.procedural_env import PackedStates
     from stratego_env_amd.vec_env import VecStrategoEnv
-    from tests.test_gpu_generic_geometry import CUSTOM
+    from tests.boards import CUSTOM
     v = CUSTOM['c7x7']
     n = 16
     env = VecStrategoEnv(v, n, seed=23, auto_reset=False, human_inits=False, placement='plain')

@@ -30,17 +30,13 @@ import numpy as np
 import pytest
 
 from tests import choose_rule as cr
+from tests.boards import _board
 
 pytestmark = pytest.mark.gpu
 
 SEED, OFFSET = 99, 3
 POISON = -7
 TOY = ('micro', 'tiny', 'c3x3', 'fives')
-
-
-def _variant(board):
-    from tests.test_gpu_generic_geometry import CUSTOM
-    return CUSTOM[board] if board in CUSTOM else board
 
 
 class _Runner:
@@ -50,7 +46,7 @@ class _Runner:
         import torch
         from stratego_env_amd.vec_env import VecStrategoEnv
         self.torch, self.board, self.n, self.na = torch, board, n, cr.n_actions(board)
-        self.env = VecStrategoEnv(_variant(board), n, seed=SEED, env_id_offset=OFFSET, auto_reset=True, compact_outputs=True)
+        self.env = VecStrategoEnv(_board(board), n, seed=SEED, env_id_offset=OFFSET, auto_reset=True, compact_outputs=True)
         assert self.env.R * self.env.Cc * self.env.K == self.na and self.env.compact_mask_words == cr.compact_words(self.na)
         self.env.reset()
         self.advance(3)

@@ -1,32 +1,19 @@
 """sgx_determinize / PackedStates.determinize on the GPU: bit for bit the numpy restatement of the rule (tests/determinize_rule.py, which
 tests/test_determinize_cpu.py holds against the oracle's rules) on every compiled-in board size, the source left alone, well-formed records,
 the refusals (all host-side, before any launch) and one large run with the invariants checked on the device."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 from stratego_env_amd.config import VARIANTS
 from tests import determinize_rule as dr
+from tests.pool_roots import _live_env, _np
 
 pytestmark = pytest.mark.gpu
 
 BOARDS = ['standard', 'barrage', 'standard2', 'octa_barrage', 'medium', 'fives', 'tiny', 'micro']     # 10x10, 10x10, 15x15, 8x8, 6x6, 5x5, 4x4, 3x4
 DRAWS = (0, 1, 1 << 40)
 SGX_EINVAL = -1
-
-
-def _live_env(name, n, steps, seed):
-    from stratego_env_amd.vec_env import VecStrategoEnv
-    env = VecStrategoEnv(name, n, seed=seed, auto_reset=True, placement='plain')
-    env.reset()
-    env.rollout_steps(steps)
-    return env
-
-
-def _np(t):
-    return t.cpu().numpy()
 
 
 @pytest.mark.parametrize('name', BOARDS)
@@ -76,7 +63,7 @@ def test_hidden_counts_land_between_guard_bands(name):
     inside is."""
     import torch
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena, I32_PHASES
+    from tests.guard_bands import Arena, I32_PHASES
     n = 37
     env = _live_env(name, n, 25, seed=4)
     states, players = (_np(t) for t in env.export_state())
@@ -134,7 +121,7 @@ def test_in_place_and_the_int64_api():
     included) equals the packed path and the restatement."""
     import torch
     from stratego_env_amd.procedural_env import BatchedStrategoProceduralEnv
-    from tests.test_gpu_procedural import _sample_states
+    from tests.pool_roots import _sample_states
     for name in ('barrage', 'tiny'):
         n = 48
         states, players = _sample_states(name, n, np.random.RandomState(13))

@@ -7,8 +7,8 @@ import pytest
 
 from stratego_env_amd.config import VARIANTS
 from tests import determinize_weighted_rule as wr
-from tests.test_determinize_weighted_cpu import (chi2_against, fives_samples, one_hot_truth, skewed_fives_table, third_zero_table)
-from tests.test_gpu_determinize import _live_env, _np
+from tests.pool_roots import _live_env, _np
+from tests.tables import chi2_against, fives_samples, one_hot_truth, skewed_fives_table, third_zero_belief
 
 pytestmark = pytest.mark.gpu
 
@@ -24,8 +24,8 @@ def _tables(cells, n_src):
     big[rs.random_sample(big.shape) < 0.25] = 0
     big_each = rs.randint(0, 65536, size=(n_src, 2, 12, cells))
     big_each[rs.random_sample(big_each.shape) < 0.4] = 0
-    return [('shared, a third zero', third_zero_table(cells, seed=1).astype(np.int64), True),
-            ('per record, a third zero', third_zero_table(cells, seed=2, shape=(n_src, 2, 12, cells)).astype(np.int64), False),
+    return [('shared, a third zero', third_zero_belief(cells, seed=1).astype(np.int64), True),
+            ('per record, a third zero', third_zero_belief(cells, seed=2, shape=(n_src, 2, 12, cells)).astype(np.int64), False),
             ('shared, entries to 65,535', big.astype(np.int64), True),
             ('all zero', np.zeros((2, 12, cells), dtype=np.int64), True),
             ('per record, entries to 65,535', big_each.astype(np.int64), False)]
@@ -87,7 +87,7 @@ def test_bit_exact_on_boards_of_many_slices(name):
     import torch
     from stratego_env_amd import config
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_generic_geometry import CUSTOM
+    from tests.boards import CUSTOM
     config.VARIANTS[name] = CUSTOM[name]
     try:
         v = CUSTOM[name]
@@ -118,15 +118,15 @@ def test_in_place_and_the_int64_api():
     path and the restatement; hidden_dev and off_belief_dev are nullable; the Python checks of `beliefs`."""
     import torch
     from stratego_env_amd.procedural_env import BatchedStrategoProceduralEnv
-    from tests.test_gpu_procedural import _sample_states
+    from tests.pool_roots import _sample_states
     for name in ('barrage', 'tiny'):
         v = VARIANTS[name]
         cells = v.rows * v.columns
         n = 48
         states, players = _sample_states(name, n, np.random.RandomState(13))
         pe = BatchedStrategoProceduralEnv(name, n)
-        shared = third_zero_table(cells, seed=4)
-        each = third_zero_table(cells, seed=5, shape=(n, 2, 12, cells))
+        shared = third_zero_belief(cells, seed=4)
+        each = third_zero_belief(cells, seed=5, shape=(n, 2, 12, cells))
         for observer, draw, table in ((0, 0, shared), (1, 3, each), (-1, 1 << 40, shared)):
             want, want_hidden, want_off = wr.determinize_weighted_batch(states, players, observer, table, 0, 0, draw)
             table_t = torch.from_numpy(table.astype(np.int64)).cuda()
@@ -208,7 +208,7 @@ def test_an_inconsistent_record_is_copied_unchanged():
         states.append(st)
     states = np.stack(states)
     players = np.ones(n, dtype=np.int8)
-    table = third_zero_table(25, seed=8)
+    table = third_zero_belief(25, seed=8)
     pe = BatchedStrategoProceduralEnv('fives', n)
     got, hidden, off = pe.determinize(states, players, observer=1, draw=9, beliefs=table, return_off_belief=True)
     want, want_hidden, want_off = wr.determinize_weighted_batch(states, players, 1, table, 0, 0, 9)
@@ -224,7 +224,7 @@ def test_65536_samples_of_the_fives_position(kind):
     of zeros, bit-exact against the restatement's samples -- so the chi-squared is the CPU test's."""
     import torch
     from stratego_env_amd.procedural_env import BatchedStrategoProceduralEnv, PackedStates
-    from tests.test_determinize_cpu import fives_position
+    from tests.pool_roots import fives_position
     st, worlds = fives_position()
     n = 65536
     table = np.full((2, 12, 25), 7, dtype=np.uint16) if kind == 'constant' else skewed_fives_table()
@@ -255,7 +255,7 @@ def test_outputs_and_table_between_guard_bands(name):
     what they were.  (dst's records are the library's own allocation: they are held to the restatement byte for byte instead.)"""
     import torch
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena, I32_PHASES
+    from tests.guard_bands import Arena, I32_PHASES
     v = VARIANTS[name]
     cells = v.rows * v.columns
     n = 37
@@ -265,7 +265,7 @@ def test_outputs_and_table_between_guard_bands(name):
     vec = pool._vec
     for k, phase in enumerate(I32_PHASES):
         shared = k % 2 == 0
-        table = third_zero_table(cells, seed=30 + k, shape=(2, 12, cells) if shared else (n, 2, 12, cells))
+        table = third_zero_belief(cells, seed=30 + k, shape=(2, 12, cells) if shared else (n, 2, 12, cells))
         ar_h = Arena('hidden', (n,), torch.int32, phase, vec.device)
         ar_o = Arena('off_belief', (n,), torch.int32, I32_PHASES[(k + 1) % 4], vec.device)
         ar_b = Arena('belief', table.shape, torch.int16, I32_PHASES[(k + 2) % 4], vec.device)

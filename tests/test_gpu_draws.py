@@ -143,7 +143,7 @@ def test_start_pool_rows_and_first_movers():
     """np.random.randint over the pool and a fair coin for the first mover (maenv:519-527), per game: 16 distinguishable records on Micro,
     first_player='random', auto-reset; the rows and first movers of the first four games of every env."""
     from stratego_env_amd.config import VARIANTS
-    from tests.test_start_pool_cpu import make_pool
+    from tests.pool_roots import make_pool
     n_pool, games, chunk = 16, 4, 32
     states, players = make_pool(VARIANTS['micro'], 2, n=n_pool)
     assert len({s.tobytes() for s in states}) == n_pool

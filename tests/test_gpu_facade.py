@@ -6,6 +6,7 @@ import pytest
 
 from stratego_env_amd import GameVersions, ObservationModes
 from stratego_env_amd.config import VARIANTS
+from tests.boards import _state_from_maps
 from tests.helpers import digest_obs, load_expanded, load_games
 
 pytestmark = pytest.mark.gpu
@@ -18,16 +19,6 @@ def _env(name, **kw):
     cfg = {'version': GameVersions(name), 'observation_mode': ObservationModes.PARTIALLY_OBSERVABLE}
     cfg.update(kw)
     return StrategoMultiAgentEnv(cfg)
-
-
-def _state_from_maps(name, m1, m2):
-    from oracle import oracle as orc
-    from stratego_env_amd.config import VARIANTS
-    v = VARIANTS[name]
-    ob = np.zeros((v.rows, v.columns), dtype=np.int64)
-    for r, c in v.obstacle_locations:
-        ob[r, c] = 1
-    return orc.OracleRules(v.rows, v.columns).create_initial_state(ob, m1.astype(np.int64), m2.astype(np.int64), v.max_turns)
 
 
 @pytest.mark.parametrize('name', ['barrage', 'standard', 'tiny', 'micro', 'octa_barrage'])

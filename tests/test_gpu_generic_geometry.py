@@ -7,48 +7,23 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from stratego_env_amd import config
 from stratego_env_amd.config import custom_variant
+from tests.boards import CUSTOM, registered
 from tests.helpers import oracle_cvariant, oracle_env
+from tests.step_checks import check_step_vs_oracle
 
 pytestmark = pytest.mark.gpu
-
-#                                                        spy scout miner sgt lt cpt maj col gen mar flag bomb
-CUSTOM = {
-    'c3x3': custom_variant(3, 3, max_turns=24, piece_counts=(0, 1, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0), name='c3x3'),
-    'c7x7': custom_variant(7, 7, max_turns=150, obstacle_locations=((3, 1), (3, 5)),
-                           piece_counts=(1, 2, 1, 0, 1, 1, 0, 1, 0, 1, 1, 2), initial_state_usable_rows=2, name='c7x7'),
-    'c9x5': custom_variant(9, 5, max_turns=200, obstacle_locations=((4, 2),),
-                           piece_counts=(1, 3, 2, 1, 1, 1, 1, 0, 1, 1, 1, 2), initial_state_usable_rows=3, name='c9x5'),
-    'c12x12': custom_variant(12, 12, max_turns=300, obstacle_locations=((5, 2), (6, 2), (5, 3), (6, 3), (5, 8), (6, 8), (5, 9), (6, 9)),
-                             piece_counts=(1, 8, 5, 4, 4, 4, 3, 2, 1, 1, 1, 6), initial_state_usable_rows=4, name='c12x12'),
-    'c3x40': custom_variant(3, 40, max_turns=120, piece_counts=(1, 6, 2, 1, 1, 1, 1, 1, 1, 1, 1, 3), name='c3x40'),   # K = 83 > 64 lanes
-    # more than 256 cells: 10-bit cell indices in the packed record (uint32 capture events, 6-bit recent-move codes), templates read from
-    # global memory, records staged in a loop
-    'c20x20': custom_variant(20, 20, max_turns=400, obstacle_locations=((9, 4), (10, 4), (9, 5), (10, 5), (9, 14), (10, 14), (9, 15), (10, 15)),
-                             piece_counts=(1, 8, 5, 4, 4, 4, 3, 2, 1, 1, 1, 6), initial_state_usable_rows=3, name='c20x20'),
-    'c32x32': custom_variant(32, 32, max_turns=250, obstacle_locations=((15, 7), (16, 7), (15, 24), (16, 24)),      # SGX_MAX_CELLS
-                             piece_counts=(1, 8, 5, 4, 4, 4, 3, 2, 1, 1, 1, 6), initial_state_usable_rows=2, name='c32x32'),
-    'c17x16': custom_variant(17, 16, max_turns=300, obstacle_locations=((8, 3), (8, 12)),
-                             piece_counts=(1, 6, 3, 2, 2, 2, 2, 1, 1, 1, 1, 4), initial_state_usable_rows=2, name='c17x16'),
-}
 
 
 @pytest.fixture(autouse=True)
 def _custom_names():
-    """The shared checkers look variants up by name: register the test-only names for the duration of a test (the product
-    takes the Variant objects themselves)."""
-    config.VARIANTS.update(CUSTOM)
-    yield
-    for k in CUSTOM:
-        config.VARIANTS.pop(k, None)
+    yield from registered(CUSTOM)
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps', [('c3x3', 48, 80), ('c7x7', 32, 200), ('c9x5', 32, 200), ('c12x12', 12, 250), ('c3x40', 12, 120),
                                                  ('c20x20', 6, 300), ('c17x16', 8, 250), ('c32x32', 3, 160)])
 def test_step_mode_bit_exact_vs_oracle(name, n_envs, n_steps):
-    from tests.test_gpu_parity import test_step_bit_exact_vs_oracle
-    test_step_bit_exact_vs_oracle(name, n_envs, n_steps, 0.1)
+    check_step_vs_oracle(name, n_envs, n_steps, 0.1)
 
 
 def _sampled_states(name, n, seed):

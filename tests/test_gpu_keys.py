@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import keys_rule as kr
-from tests.test_gpu_playout import CASES, N_SRC, _np, _roots
+from tests.pool_roots import CASES, N_SRC, _np, _roots
 
 pytestmark = pytest.mark.gpu
 
@@ -91,7 +91,7 @@ def test_ragged_sizes(name, per_workgroup):
 def test_a_wide_board():
     """20 x 20: 10-bit cell indices, 32-bit capture events, a record of several KiB walked in a loop"""
     from stratego_env_amd.vec_env import VecStrategoEnv
-    from tests.test_gpu_generic_geometry import CUSTOM
+    from tests.boards import CUSTOM
     v = CUSTOM['c20x20']
     n = 6
     env = VecStrategoEnv(v, n, seed=23, auto_reset=False, human_inits=False, placement='plain')
@@ -108,7 +108,7 @@ def test_chained_capture_events():
     """many66 (nine scouts a side): a count beyond 8 on one cell is several events of one key in the record and ONE feature, the sum, in the key"""
     import torch
     from stratego_env_amd.vec_env import VecStrategoEnv
-    from tests.test_gpu_many_pieces import CUSTOM
+    from tests.boards import MANY_PIECES as CUSTOM
     v = CUSTOM['many66']
     counts = (7, 8, 9, 16, 17)
     n = len(counts)
@@ -180,7 +180,7 @@ def test_with_the_librarys_own_calls(name):
 @pytest.mark.parametrize('name', ['fives', 'barrage'])          # two records per wave / one
 def test_guard_bands(name):
     import torch
-    from tests.test_gpu_guard_bands import Arena
+    from tests.guard_bands import Arena
     env, states, players, _ = _roots(name, CASES[name][0])
     L = env._L
     idx = np.random.RandomState(2).randint(0, N_SRC, size=37).astype(np.int32)

@@ -4,8 +4,8 @@ kernel -- and, output by output, against the wave-per-game kernel on the same in
 import numpy as np
 import pytest
 
-from stratego_env_amd import config
 from stratego_env_amd.config import custom_variant
+from tests.boards import registered
 
 pytestmark = pytest.mark.gpu
 
@@ -22,10 +22,7 @@ CUSTOM = {
 
 @pytest.fixture(autouse=True)
 def _custom_names():
-    config.VARIANTS.update(CUSTOM)
-    yield
-    for k in CUSTOM:
-        config.VARIANTS.pop(k, None)
+    yield from registered(CUSTOM)
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps', [('micro', 64, 150), ('micro', 200, 60), ('tiny', 64, 250), ('tiny', 130, 120),
@@ -33,8 +30,8 @@ def _custom_names():
 def test_lane_kernel_step_bit_exact_vs_oracle(name, n_envs, n_steps):
     """tests/test_gpu_parity.py's step-by-step comparison (mask, observation, rewards, flags, sampler, int64 state; 10 % garbage
     actions; auto-reset) without terminal-observation buffers, i.e. on the lane kernel."""
-    from tests.test_gpu_parity import test_step_bit_exact_vs_oracle
-    test_step_bit_exact_vs_oracle(name, n_envs, n_steps, 0.1, seed_salt=3, final_obs=False, lane_kernel=True)
+    from tests.step_checks import check_step_vs_oracle
+    check_step_vs_oracle(name, n_envs, n_steps, 0.1, seed_salt=3, final_obs=False, lane_kernel=True)
 
 
 @pytest.mark.parametrize('name,n', [('micro', 1), ('micro', 63), ('micro', 65), ('micro', 4097), ('tiny', 1000), ('zoo44', 777), ('thirds44', 513)])

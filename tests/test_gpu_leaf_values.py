@@ -2,21 +2,23 @@
 values of every position that is not over -- bit for bit the restatement (the playout / weighted / replay / children rule modules as they are,
 the rewards of the slots that are not over then replaced by tests/leaf_values_rule.py on the final states), in both views -- and nothing else
 changes: every other output and every record is what the same call writes with the table cleared.  Off means off, wave-mates, the setter's
-semantics (two tables on one stream, the refusals, guard bands, a gated stream) and what it is for: a greedy one-ply choice and a truncated
-PIMC that see a capture.
+semantics (two tables on one stream, the refusals, guard bands; the gated stream is the row `playout-leaf-values` of tests/stream_cases.py)
+and what it is for: a greedy one-ply choice and a truncated PIMC that see a capture.
 
-Roots are taken as tests/test_gpu_playout.py takes them (rollouts without auto-reset, its rollout lengths and caps), so finished and unfinished
-roots mix; the two boards outside its table get roots from three rollouts -- to the max-turn ending, one move short of it, and a short one --
-so that every cap leaves slots cut off and slots finished (counted per cap over the launches of a test: on Micro one weighted launch
-finishes all of its 29 games within 7 moves).  The table is random int16 over the full range with distinct entries: a wrong cell, row or view
-cannot cancel."""
+Roots are taken as tests/test_gpu_playout.py takes them (tests/pool_roots.py: rollouts without auto-reset, its rollout lengths and caps), so
+finished and unfinished roots mix; the two boards outside its table get roots from three rollouts -- to the max-turn ending, one move short
+of it, and a short one -- so that every cap leaves slots cut off and slots finished (counted per cap over the launches of a test: on Micro
+one weighted launch finishes all of its 29 games within 7 moves).  The table is random int16 over the full range with distinct entries: a
+wrong cell, row or view cannot cancel."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from tests import children_rule as cr, leaf_values_rule as lv, playout_rule as pr, replay_rule as rr, test_gpu_playout as tp, weighted_playout_rule as wr
-from tests.test_weighted_playout_cpu import third_zero_table
+from tests import children_rule as cr, leaf_values_rule as lv, playout_rule as pr, pool_roots as tp, replay_rule as rr, weighted_playout_rule as wr
+from tests.boards import _board
+from tests.pool_roots import _np
+from tests.tables import third_zero_table
 
 pytestmark = pytest.mark.gpu
 
@@ -31,23 +33,9 @@ WEIGHTS = third_zero_table(0)
 BOARDS = {'micro': ('micro', None), 'tiny': ('tiny', None), 'fives': ('fives', None), 'medium': ('medium', None), 'octa_barrage': ('octa_barrage', None),
           'barrage-one-game-per-wave': ('barrage', False), 'barrage-two-games-per-wave': ('barrage', True), 'standard2': ('standard2', None),
           'c20x20': ('c20x20', None), 'many66': ('many66', None)}
-# the boards outside tests/test_gpu_playout.py's table: (the steps of three rollouts of eight games -- to the max-turn ending, one move
+# the boards outside tests/pool_roots.py's CASES: (the steps of three rollouts of eight games -- to the max-turn ending, one move
 # short of it, and a short one --, caps)
 THREE_ROLLOUTS = {'c20x20': ((400, 399, 40), (1, 7)), 'many66': ((120, 119, 30), (1, 7))}
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _variant(key):
-    if key == 'c20x20':
-        from tests.test_gpu_generic_geometry import CUSTOM
-        return CUSTOM[key]
-    if key == 'many66':
-        from tests.test_gpu_many_pieces import CUSTOM
-        return CUSTOM[key]
-    return key
 
 
 def _cells(v):
@@ -66,7 +54,7 @@ class Roots:
     def __init__(self, board):
         from stratego_env_amd.procedural_env import PackedStates
         key, self.half_wave = BOARDS[board]
-        self.v = v = _variant(key)
+        self.v = v = _board(key)
         self.owned = []
         if key in tp.CASES:
             steps, caps, _ = tp.CASES[key]
@@ -419,18 +407,16 @@ def test_guard_bands_only_the_rewards_differ():
     outside the payloads is written, and a NULL reward pointer writes nothing more"""
     import torch
     from stratego_env_amd import _lib
-    from tests.test_gpu_guard_bands import Arena
+    from tests.guard_bands import pool_arenas
     R = Roots('fives')
     n = N_SRC
     pool = R.pool(n)
     vec = pool._vec
     L = vec._L
     src_h = R.src._h if hasattr(R.src, '_h') else R.src._vec._h
-    dtypes = {'float32': torch.float32, 'uint8': torch.uint8, 'int8': torch.int8, 'int32': torch.int32}
 
     def arenas(byte_phase, word_phase):
-        return {k: Arena(k, (n, w) if w > 1 else (n,), dtypes[t], word_phase if t in ('float32', 'int32') else byte_phase, vec.device)
-                for k, w, t in tp.OUT_SPECS}
+        return pool_arenas(tp.PLAYOUT_OUT_SPECS, n, vec.device, byte_phase, word_phase)
 
     def call(ptrs):
         io = _lib.SgxPlayoutIO(ptrs['reward'], ptrs['done'], ptrs['ending_invalid'], ptrs['player'], ptrs['length'], 3, 0)
@@ -465,24 +451,6 @@ def test_guard_bands_only_the_rewards_differ():
         else:
             assert a.host().tobytes() == host[True][k].tobytes(), k
     R.close()
-
-
-def test_a_playout_with_a_table_returns_before_its_stream_drains():
-    """the gate of tests/stream_gate.py around sgx_playout with leaf values set on dst: all its work on the caller's stream, no wait"""
-    import torch
-    from tests import stream_gate as sg, test_gpu_streams as ts
-    torch.cuda.set_device(0)
-    case = sg.Case(sg.material('barrage', ts.N_BARRAGE))
-    ts._playout(False)(case)
-    dst = case.handles[1][0]                                                   # (_pools: src first, then dst)
-    L = case.M.L
-    T = _table(100)
-    assert L.sgx_set_leaf_values(dst._h, T.ctypes.data_as(C.c_void_p), LIMIT, DENOM, 0) == 0, L.sgx_last_error()
-    assert L.sgx_leaf_values_set(dst._h) == 1
-    reward, done = case.outputs[0], case.outputs[1]
-    sg.run_case(case, may_wait=False, label='playout with leaf values')
-    open_ = done == 0
-    assert bool(open_.any()) and bool((reward[open_] != 0).any()), "cut-off playouts carry values"
 
 
 def _capture_position():

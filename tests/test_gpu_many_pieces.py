@@ -5,31 +5,20 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from stratego_env_amd import config
-from stratego_env_amd.config import custom_variant
+from tests.boards import MANY_PIECES as CUSTOM, registered
+from tests.step_checks import check_step_vs_oracle
 
 pytestmark = pytest.mark.gpu
-
-#                                                                    spy scout miner sgt lt cpt maj col gen mar flag bomb
-CUSTOM = {
-    'many66': custom_variant(6, 6, max_turns=120, piece_counts=(0, 9, 1, 0, 0, 0, 0, 0, 0, 0, 1, 1), initial_state_usable_rows=2, name='many66'),
-    'many88': custom_variant(8, 8, max_turns=160, obstacle_locations=((3, 2), (4, 5)), piece_counts=(1, 12, 2, 0, 0, 0, 0, 0, 0, 1, 1, 3),
-                             initial_state_usable_rows=3, name='many88'),
-}
 
 
 @pytest.fixture(autouse=True)
 def _custom_names():
-    config.VARIANTS.update(CUSTOM)
-    yield
-    for k in CUSTOM:
-        config.VARIANTS.pop(k, None)
+    yield from registered(CUSTOM)
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps', [('many66', 48, 300), ('many88', 32, 300)])
 def test_step_parity_with_more_than_eight_pieces_of_a_type(name, n_envs, n_steps):
-    from tests.test_gpu_parity import test_step_bit_exact_vs_oracle
-    test_step_bit_exact_vs_oracle(name, n_envs, n_steps, 0.1, seed_salt=5)
+    check_step_vs_oracle(name, n_envs, n_steps, 0.1, seed_salt=5)
 
 
 @pytest.mark.parametrize('channel_mode', ['extended', 'original'])

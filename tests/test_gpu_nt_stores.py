@@ -10,11 +10,10 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from stratego_env_amd import config
 from stratego_env_amd import setups as S
 from stratego_env_amd.config import VARIANTS
+from tests.boards import CUSTOM, registered
 from tests.helpers import oracle_cvariant
-from tests.test_gpu_generic_geometry import CUSTOM
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +26,7 @@ def nt_forced(monkeypatch):
 
 @pytest.fixture
 def custom_names():
-    config.VARIANTS.update(CUSTOM)
-    yield
-    for k in CUSTOM:
-        config.VARIANTS.pop(k, None)
+    yield from registered(CUSTOM)
 
 
 def _table(name):
@@ -47,21 +43,21 @@ def test_step_parity_with_nt_forced(nt_forced, name, n_envs, n_steps, garbage):
     """Every output of every step (and the terminal observations) with all whole lines leaving as non-temporal stores.
     standard / standard2 run long enough for captured miners / majors / bombs / colonels: values without a 4-bit code, written by
     patch_uncoded (4-aligned boards) / patch_uncoded_floats after s_waitcnt (odd boards) next to NT bulk stores."""
-    from tests.test_gpu_parity import test_step_bit_exact_vs_oracle
-    test_step_bit_exact_vs_oracle(name, n_envs, n_steps, garbage, seed_salt=3)
+    from tests.step_checks import check_step_vs_oracle
+    check_step_vs_oracle(name, n_envs, n_steps, garbage, seed_salt=3)
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps', [('c3x3', 48, 80), ('c7x7', 32, 200), ('c9x5', 32, 200), ('c12x12', 12, 250), ('c3x40', 12, 120),
                                                  ('c20x20', 4, 200)])
 def test_custom_geometries_with_nt_forced(nt_forced, custom_names, name, n_envs, n_steps):
-    from tests.test_gpu_parity import test_step_bit_exact_vs_oracle
-    test_step_bit_exact_vs_oracle(name, n_envs, n_steps, 0.1, seed_salt=4)
+    from tests.step_checks import check_step_vs_oracle
+    check_step_vs_oracle(name, n_envs, n_steps, 0.1, seed_salt=4)
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps', [('barrage', 32, 400), ('standard', 6, 400), ('tiny', 48, 150), ('micro', 48, 80),
                                                  ('fives', 32, 150), ('octa_barrage', 16, 200), ('medium', 16, 150), ('standard2', 2, 200)])
 def test_both_observations_with_nt_forced(nt_forced, name, n_envs, n_steps):
-    from tests.test_gpu_full_obs import check_both_obs_vs_oracle
+    from tests.step_checks import check_both_obs_vs_oracle
     check_both_obs_vs_oracle(name, n_envs, n_steps, 'extended')
 
 
@@ -69,14 +65,14 @@ def test_both_observations_with_nt_forced(nt_forced, name, n_envs, n_steps):
                                                  ('standard2', 2, 60)])
 def test_original_channels_with_nt_forced(nt_forced, name, n_envs, n_steps):
     """(the 'original' kinds keep the LUT emission with plain stores: the switch must leave them alone)"""
-    from tests.test_gpu_full_obs import check_both_obs_vs_oracle
+    from tests.step_checks import check_both_obs_vs_oracle
     check_both_obs_vs_oracle(name, n_envs, n_steps, 'original')
 
 
 def test_functional_api_with_nt_forced(nt_forced):
-    from tests.test_gpu_procedural import test_functional_api_matches_oracle
+    from tests.step_checks import check_functional_api_vs_oracle
     for name in ('barrage', 'fives'):
-        test_functional_api_matches_oracle(name)
+        check_functional_api_vs_oracle(name)
 
 
 @pytest.mark.parametrize('name,n', [('barrage', 3000), ('barrage', 1), ('barrage', 9), ('fives', 2001), ('micro', 5003), ('standard2', 300)])

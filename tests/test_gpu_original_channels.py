@@ -9,9 +9,9 @@ from oracle import oracle as orc
 from stratego_env_amd import GameVersions, ObservationModes
 from stratego_env_amd.config import VARIANTS
 from tests.helpers import GOLDEN, _load_npz, oracle_cvariant
-from tests.test_gpu_full_obs import check_both_obs_vs_oracle
-from tests.test_gpu_parity import _table
-from tests.test_oracle_golden_both import digest_both
+from tests.step_checks import check_both_obs_vs_oracle
+from tests.boards import _table
+from tests.step_checks import digest_both
 
 pytestmark = pytest.mark.gpu
 MASK, POBS, FOBS = 'valid_actions_mask', 'partial_observation', 'full_observation'
@@ -63,7 +63,7 @@ def test_original_partial_only_bit_exact_vs_oracle(name, n_envs, n_steps):
 @pytest.mark.parametrize('name', ['barrage', 'tiny', 'micro', 'fives', 'octa_barrage'])
 def test_facade_original_mode_replays_reference_goldens(name):
     from stratego_env_amd.multiagent_env import StrategoMultiAgentEnv
-    from tests.test_gpu_facade import _state_from_maps
+    from tests.boards import _state_from_maps
     g = _load_npz(os.path.join(GOLDEN, 'games_orig_%s.npz' % name))
     env = StrategoMultiAgentEnv({'version': GameVersions(name), 'obs_channel_mode': 'original'})    # BOTH is the default mode
     assert env.observation_space.spaces[POBS].shape == (env.rows, env.columns, 32)

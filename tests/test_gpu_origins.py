@@ -13,8 +13,7 @@ import numpy as np
 import pytest
 
 from tests import origins_rule as orr
-from tests.test_gpu_playout import CASES, N_SRC, _np, _roots
-from tests.test_gpu_replay import GOLDEN, LPG, _golden, _golden_roots, _layouts, _ragged_lists, _results
+from tests.pool_roots import CASES, GOLDEN, LPG, N_SRC, _golden, _golden_roots, _layouts, _np, _ragged_lists, _replay_results, _roots
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +45,7 @@ def _record_bytes(pool):
 
 
 def _same_but_for_the_labels(tracked_pool, tracked, plain_pool, plain, where):
-    a, b = _results(tracked), _results(plain)
+    a, b = _replay_results(tracked), _replay_results(plain)
     for k in a:
         assert a[k].tobytes() == b[k].tobytes(), (where, k)
     assert _record_bytes(tracked_pool) == _record_bytes(plain_pool), where
@@ -206,7 +205,7 @@ def test_guard_bands_around_the_labels(name):
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena
+    from tests.guard_bands import Arena
     states, players, finished, idx, sp, d1, lengths, given = _material(name)
     env = _roots(name, CASES[name][0])[0]
     cells = states[0][0].size

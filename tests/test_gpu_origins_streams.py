@@ -1,56 +1,11 @@
 """The tracked replay (sgx_set_replay_origins + sgx_replay) under the header's stream contract: the label work goes to the
-call's stream like the rest and the call does not wait.  One case of the gate harness (tests/stream_gate.py), built like the `replay` row of
-tests/test_gpu_streams.py -- the setter takes no stream and launches nothing, so the call under test is sgx_replay with the setting on --
-and one data-only check of the Python wrapper."""
-import ctypes as C
-
+call's stream like the rest and the call does not wait.  The case of the gate harness is the row `replay-tracked` of the one table
+(tests/stream_cases.py, run by tests/test_gpu_streams.py); here is the data-only check of the Python wrapper."""
 import pytest
 
+from tests.stream_cases import N_BARRAGE, _labels
+
 pytestmark = pytest.mark.gpu
-
-N_BARRAGE = 17                                     # one workgroup's games plus 1, as tests/test_gpu_streams.py takes it
-CELLS = 100
-
-
-def _labels(n, seed):
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    return torch.randint(-32768, 32768, (n, 2, CELLS), generator=g, dtype=torch.int16).cuda()
-
-
-def _replay_tracked(c):
-    import torch
-    from stratego_env_amd import _lib
-    from tests.test_gpu_streams import _chk, _p, _pools
-    M, L, n, LEN = c.M, c.M.L, c.M.n, 4
-    dst, src, si, idx = _pools(c)
-    lists = {}
-    for X in 'AB':
-        first = M.act[X][idx[X].long()]                    # each root's own valid action, then entries that are mostly invalid (skipped)
-        lists[X] = torch.stack([first] + [first.roll(k) for k in range(1, LEN)], 1).contiguous()
-    acts = c.inp(lists['A'], lists['B'])                   # written on S
-    origin_in = c.inp(_labels(n, 1), _labels(n, 2))        # a staged input: written on S behind the gate
-    origin_out = c.new((n, 2, CELLS), torch.int16)         # a compared output
-    ap, co, stop = c.new((n,), torch.int32), c.new((n,), torch.int32), c.new((n,), torch.uint8)
-    rew, done, einv, pl = c.new((n, 2), torch.float32), c.new((n,), torch.uint8), c.new((n,), torch.uint8), c.new((n,), torch.int8)
-    io = _lib.SgxReplayIO(acts.data_ptr(), None, ap.data_ptr(), co.data_ptr(), stop.data_ptr(), rew.data_ptr(), done.data_ptr(), einv.data_ptr(),
-                          pl.data_ptr(), LEN, 1, n * LEN, LEN, _lib.REPLAY_SKIP_INVALID)
-    _chk(c, L.sgx_set_replay_origins(dst._h, _p(origin_in), _p(origin_out)))      # (the setting: no stream, no launch)
-
-    def call(sp, s):
-        _chk(c, L.sgx_replay(dst._h, src._h, _p(si), C.byref(io), sp))
-        assert L.sgx_last_launch_kind(dst._h) == _lib.LAUNCH_REPLAY_TRACKED
-    c.call = call
-
-
-def test_tracked_replay_runs_on_its_stream_and_does_not_wait():
-    """Twin, gated run and NULL-stream control (run_case asserts that the control mismatches); not may_wait."""
-    import torch
-    from tests import stream_gate as sg
-    torch.cuda.set_device(0)
-    case = sg.Case(sg.material('barrage', N_BARRAGE))
-    _replay_tracked(case)
-    sg.run_case(case, may_wait=False, label='replay-tracked')
 
 
 def test_the_python_wrapper_passes_the_current_stream():

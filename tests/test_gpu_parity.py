@@ -5,27 +5,13 @@ import pytest
 from oracle import oracle as orc
 from stratego_env_amd import setups as S
 from stratego_env_amd.config import VARIANTS
+from tests.boards import _table
 from tests.helpers import digest_obs, load_games, oracle_cvariant, oracle_env
+from tests.step_checks import _oracle_batch, check_step_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
 MASK, POBS = 'valid_actions_mask', 'partial_observation'
-
-
-def _table(name):
-    v = VARIANTS[name]
-    return S.load_setup_table(v.human_inits) if v.human_inits else None
-
-
-def _oracle_batch(name, seed, g0, n):
-    cv = oracle_cvariant(name, setups=_table(name))
-    envs = []
-    for e in range(n):
-        oe = oracle_env(name)
-        oe.reset(initial_state_override=orc.reset_state(cv, seed, g0 + e, 0))
-        oe.game_no = 0
-        envs.append(oe)
-    return cv, envs
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps,garbage', [
@@ -33,81 +19,10 @@ def _oracle_batch(name, seed, g0, n):
     ('medium', 32, 300, 0.1), ('fives', 32, 200, 0.1), ('tiny', 64, 200, 0.1), ('micro', 64, 120, 0.1),
     ('short_barrage', 32, 250, 0.1), ('standard2', 4, 150, 0.05),
 ])
-def test_step_bit_exact_vs_oracle(name, n_envs, n_steps, garbage, seed_salt=0, require_endings=True, final_obs=True, lane_kernel='auto', emit_obs=True):
-    """Random-valid-action rollouts with auto-reset (+ injected garbage actions): every output of every step.
-    (tools/soak_parity.py re-runs this with other seeds, batch sizes and garbage rates for minutes.)
-    emit_obs=False (with final_obs=False): the steps pass no observation pointer -- the no-observation kernel kind -- and everything
-    else (mask, rewards, flags, sampled action, exported state) is compared as before."""
-    assert emit_obs or not final_obs
-    import torch
-    from stratego_env_amd.vec_env import VecStrategoEnv
-    v = VARIANTS[name]
-    seed, g0 = 0xABCDEF12345 + len(name) + 7919 * seed_salt, 1000 + 31 * seed_salt
-    env = VecStrategoEnv(name, n_envs, seed=seed, env_id_offset=g0, auto_reset=True, final_obs=final_obs)
-    env.set_lane_kernel(lane_kernel)
-    cv, oenvs = _oracle_batch(name, seed, g0, n_envs)
-    NA = v.num_spatial_actions
-    rs = np.random.RandomState(7 + seed_salt)
-    obs, mask, player = env.reset()
-    obs_h, mask_h, player_h = obs.cpu().numpy(), mask.cpu().numpy(), player.cpu().numpy()
-    cur = []
-    for e, oe in enumerate(oenvs):
-        o = oe._obs(1)
-        assert np.array_equal(o[MASK], mask_h[e]) and o[POBS].tobytes() == obs_h[e].tobytes(), (name, 'reset', e)
-        assert player_h[e] == 1
-        cur.append(o)
-    st, pl = env.export_state()
-    assert np.array_equal(st.cpu().numpy(), np.stack([oe.state for oe in oenvs]))
-    sampled = env.sample_valid_actions().cpu().numpy()
-    games_done = 0
-    for t in range(n_steps):
-        acts = np.zeros(n_envs, dtype=np.int32)
-        for e, oe in enumerate(oenvs):
-            a = orc.sample_action(cur[e][MASK].astype(np.uint8), seed, g0 + e, oe.game_no, int(oe.state[5, 0, 0]))
-            assert sampled[e] == a, (name, t, e, 'sampler')
-            if garbage and rs.rand() < garbage:
-                a = int(rs.choice([rs.randint(NA), rs.randint(v.cells) * v.spatial_channels + v.spatial_channels - 1,
-                                   -1, NA, NA + 3, (v.cells - 1) * v.spatial_channels + rs.randint(v.spatial_channels)]))
-            acts[e] = a
-        env.step(torch.from_numpy(acts), want_next_actions=True, emit_obs=emit_obs)
-        obs_h, mask_h = env.obs.cpu().numpy(), env.mask.cpu().numpy()
-        rew_h, done_h, player_h = env.reward.cpu().numpy(), env.done.cpu().numpy(), env.player.cpu().numpy()
-        inv_h, einv_h = env.invalid_action.cpu().numpy(), env.ending_invalid.cpu().numpy()
-        fin_h = env.final_obs.cpu().numpy() if final_obs else None
-        sampled = env.next_actions.cpu().numpy()
-        for e, oe in enumerate(oenvs):
-            try:
-                o, rew, done, info = oe.step({oe.player: int(acts[e])})
-            except ValueError:
-                assert inv_h[e] == 1, (name, t, e, acts[e], 'oracle raised, GPU accepted')
-                assert not done_h[e]
-                assert np.array_equal(cur[e][MASK], mask_h[e]) and (not emit_obs or cur[e][POBS].tobytes() == obs_h[e].tobytes())
-                assert player_h[e] == oe.player
-                continue
-            assert inv_h[e] == 0, (name, t, e, acts[e], 'GPU flagged a move the oracle accepts')
-            assert bool(done_h[e]) == done['__all__'], (name, t, e)
-            if done['__all__']:
-                games_done += 1
-                assert (rew_h[e, 0], rew_h[e, 1]) == (rew[1], rew[-1]), (name, t, e, rew_h[e], rew)
-                assert bool(einv_h[e]) == info[1]['game_result_was_invalid']
-                for slot, p in ((0, 1), (1, -1)):
-                    assert fin_h is None or o[p][POBS].tobytes() == fin_h[e, slot].tobytes(), (name, t, e, 'final obs', p)
-                    assert int(o[p][MASK].sum()) == 1 and o[p][MASK][0, 0, -1] == 1
-                oe.game_no += 1
-                o = oe.reset(initial_state_override=orc.reset_state(cv, seed, g0 + e, oe.game_no))
-            else:
-                assert rew_h[e, 0] == 0 and rew_h[e, 1] == 0 and einv_h[e] == 0
-            p = oe.player
-            assert player_h[e] == p, (name, t, e)
-            assert np.array_equal(o[p][MASK], mask_h[e]), (name, t, e, 'mask')
-            assert not emit_obs or o[p][POBS].tobytes() == obs_h[e].tobytes(), (name, t, e, 'obs')
-            cur[e] = o[p]
-        if t % 50 == 49:
-            st, pl = env.export_state()
-            assert np.array_equal(st.cpu().numpy(), np.stack([oe.state for oe in oenvs])), (name, t, 'state export')
-            assert np.array_equal(pl.cpu().numpy(), np.asarray([oe.player for oe in oenvs], dtype=np.int8))
-    assert games_done > 0 or not require_endings or name in ('standard', 'standard2', 'medium_standard', 'short_standard', 'c12x12', 'c20x20', 'c17x16', 'c32x32')
-    env.close()
+def test_step_bit_exact_vs_oracle(name, n_envs, n_steps, garbage):
+    """Random-valid-action rollouts with auto-reset (+ injected garbage actions): every output of every step (tests/step_checks.py;
+    tools/soak_parity.py re-runs the checker with other seeds, batch sizes and garbage rates for minutes)."""
+    check_step_vs_oracle(name, n_envs, n_steps, garbage)
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps,garbage', [('barrage', 40, 500, 0.1), ('standard', 12, 400, 0.05), ('octa_barrage', 24, 300, 0.1),
@@ -116,7 +31,7 @@ def test_step_without_observation_bit_exact_vs_oracle(name, n_envs, n_steps, gar
     """The no-observation kernel kind (steps that pass no observation pointer: mask-only rollouts, search expansions) against the
     oracle, step by step: masks, rewards, flags, sampled actions, exported states.  (Toy boards: the lane kernel plays such launches,
     tests/test_gpu_lane_kernel.py; tests/test_gpu_no_obs_kind.py forces the wave-per-game kind there.)"""
-    test_step_bit_exact_vs_oracle(name, n_envs, n_steps, garbage, seed_salt=3, final_obs=False, emit_obs=False)
+    check_step_vs_oracle(name, n_envs, n_steps, garbage, seed_salt=3, final_obs=False, emit_obs=False)
 
 
 def test_config2_256_heldout_seeds_to_termination():

@@ -10,52 +10,19 @@ import numpy as np
 import pytest
 
 from tests import playout_rule as pr
+from tests.boards import CUSTOM
+from tests.guard_bands import pool_arenas, pool_output_sweep
+from tests.pool_roots import CASES, DRAWS, GAMES_PER_WORKGROUP, KEYS, N_SRC, PLAYOUT_OUT_SPECS, _np, _playout_results, _pool_from, _roots, _sample_states
 
 pytestmark = pytest.mark.gpu
 
 SGX_EINVAL = -1
-DRAWS = (0, 1, 1 << 40)
-KEYS = ((0, 0), (0xABCDEF0123, 1000))                    # (seed, env_id_offset) of dst
-N_SRC = 24
-# board: (rollout steps before the roots are taken, the three max_steps values: 0 = to the end where that fits the budget, else a cap,
-#         the unfinished root that 20 slots share: one whose playouts end at different lengths under the cap)
-CASES = {
-    'micro': (12, (0, 1, 7), 22),                            # 3x4, four games per wave
-    'tiny': (20, (0, 1, 7), 23),                             # 4x4, four games per wave
-    'fives': (30, (0, 1, 7), 23),                            # 5x5 (odd), two games per wave
-    'medium': (60, (0, 1, 7), 23),                           # 6x6, two games per wave (the half-wave variant)
-    'octa_barrage': (150, (1, 7, 40), 23),                   # 8x8
-    'short_barrage': (60, (0, 1, 7), 23),                    # 10x10, max_turns 100: to the end
-    'barrage': (400, (1, 7, 48), 14),                        # 10x10
-    'standard2': (400, (1, 7, 24), 17),                      # 15x15, one game per wave
-}
-GAMES_PER_WORKGROUP = {'fives': 16, 'medium': 8, 'short_barrage': 8}     # Geo::WPB x Geo::GPW of the logic-only launches
-
-
-def _np(t):
-    return t.cpu().numpy()
-
-
-def _roots(name, steps, n=N_SRC, seed=17):
-    """A live env of n games `steps` rollout steps into their games, finished games kept -> (env, states, players, finished)."""
-    from stratego_env_amd.vec_env import VecStrategoEnv
-    env = VecStrategoEnv(name, n, seed=seed, auto_reset=False, human_inits=False, placement='plain')
-    env.reset()
-    env.rollout_steps(steps, emit_obs=False, emit_mask=False)
-    states_t, players_t = env.export_state()
-    finished = _np(env.env_info()[:, 2]) != 0
-    return env, _np(states_t), _np(players_t), finished
-
-
-def _results(res):
-    return {'reward': _np(res.reward), 'done': _np(res.done), 'ending_invalid': _np(res.ending_invalid), 'player': _np(res.player),
-            'length': _np(res.length)}
 
 
 def _compare(variant, pool, res, states, players, seed, offset, draw, index, max_steps, where):
     """the pool's final states and the five result tensors against the restatement; -> the restatement's lengths"""
     want_s, want_p, want_r, want_d, want_e, want_l = pr.playout_batch(variant, states, players, seed, offset, draw, index, max_steps)
-    got = _results(res)
+    got = _playout_results(res)
     print(where, 'lengths', want_l.tolist())
     assert np.array_equal(got['length'], want_l), where
     assert got['reward'].tobytes() == want_r.tobytes(), where
@@ -127,7 +94,6 @@ def test_ragged_batches(name):
 def test_in_place_and_the_int64_api():
     import torch
     from stratego_env_amd.procedural_env import BatchedStrategoProceduralEnv, PackedStates
-    from tests.test_gpu_procedural import _sample_states
     for name, max_steps in (('fives', 0), ('barrage', 9)):
         n = 40
         states, players = _sample_states(name, n, np.random.RandomState(13))           # along golden games, terminal states included
@@ -138,16 +104,16 @@ def test_in_place_and_the_int64_api():
         res = dst.playout(src, max_steps=max_steps, draw=3)                             # pool to pool
         want_l = _compare(name, dst, res, states, players, 0, 0, 3, None, max_steps, (name, 'pool to pool'))
         assert (want_l == 0).any() and (want_l > 0).any()
-        pool_s, pool_r = _np(dst.unpack()[0]), _results(res)
+        pool_s, pool_r = _np(dst.unpack()[0]), _playout_results(res)
         res2 = src.playout(src, max_steps=max_steps, draw=3)                            # in place
         assert np.array_equal(_np(src.unpack()[0]), pool_s)
-        for k, v in _results(res2).items():
+        for k, v in _playout_results(res2).items():
             assert v.tobytes() == pool_r[k].tobytes(), (name, k)
         with pytest.raises(ValueError):
             src.playout(src, src_index=torch.zeros(n, dtype=torch.int32, device='cuda'))
         # int64 in, int64 out
         res3 = pe.playout(states, players, max_steps=max_steps, draw=3)
-        for k, v in _results(res3).items():
+        for k, v in _playout_results(res3).items():
             assert v.tobytes() == pool_r[k].tobytes(), (name, k)
         res4, final, final_players = pe.playout(states, players, max_steps=max_steps, draw=3, return_states=True)
         assert final.dtype == torch.int64 and np.array_equal(_np(final), pool_s)
@@ -160,14 +126,10 @@ def test_in_place_and_the_int64_api():
             x.close()
 
 
-OUT_SPECS = (('reward', 2, 'float32'), ('done', 1, 'uint8'), ('ending_invalid', 1, 'uint8'), ('player', 1, 'int8'), ('length', 1, 'int32'))
-
-
 def test_null_outputs_and_guard_bands():
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena
     name, n = 'fives', 37
     steps = CASES[name][0]
     env, states, players, finished = _roots(name, steps, n=n)
@@ -175,40 +137,20 @@ def test_null_outputs_and_guard_bands():
     vec = pool._vec
     L = vec._L
     want = dict(zip(('state', 'player', 'reward', 'done', 'ending_invalid', 'length'), pr.playout_batch(name, states, players, 2, 7, 5)))
-    dtypes = {'float32': torch.float32, 'uint8': torch.uint8, 'int8': torch.int8, 'int32': torch.int32}
 
-    def arenas(byte_phase, word_phase):
-        return {k: Arena(k, (n, w) if w > 1 else (n,), dtypes[t], word_phase if t in ('float32', 'int32') else byte_phase, vec.device)
-                for k, w, t in OUT_SPECS}
-
-    def call(ptrs):
+    def call(ptrs, ins=None):
         io = _lib.SgxPlayoutIO(ptrs['reward'], ptrs['done'], ptrs['ending_invalid'], ptrs['player'], ptrs['length'], 0, 0)
         return L.sgx_playout(vec._h, env._h, None, io, 5, vec._stream())
 
-    # the five tensors between guard bands, at every phase the contract allows
-    for byte_phase, word_phase in ((0, 0), (1, 4), (3, 12), (13, 0)):
-        ar = arenas(byte_phase, word_phase)
-        assert call({k: a.t.data_ptr() for k, a in ar.items()}) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        for k, a in ar.items():
-            a.check_guards('sgx_playout')
-            a.check_written('sgx_playout')
-            assert a.host().tobytes() == want[k].tobytes(), (k, byte_phase, word_phase)
-        assert np.array_equal(_np(pool.unpack()[0]), want['state'])
-    # each result pointer NULL in turn: the others are still right
-    for skip in [k for k, _, _ in OUT_SPECS]:
-        ar = arenas(0, 0)
-        assert call({k: (None if k == skip else a.t.data_ptr()) for k, a in ar.items()}) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        for k, a in ar.items():
-            a.check_guards('sgx_playout')
-            if k == skip:
-                a.check_untouched('sgx_playout')
-            else:
-                assert a.host().tobytes() == want[k].tobytes(), (k, 'without', skip)
+    def after_call(ins, skip):
+        if skip is None:
+            assert np.array_equal(_np(pool.unpack()[0]), want['state'])
+
+    # the five tensors between guard bands, at every phase the contract allows; then each result pointer NULL in turn: the others are still right
+    pool_output_sweep(PLAYOUT_OUT_SPECS, vec.device, lambda byte_phase, word_phase: {}, call, want, 'sgx_playout', after_call)
     # the phases the contract refuses: SGX_EINVAL, nothing launched
     for bad, phase in (('reward', 1), ('reward', 2), ('length', 2), ('length', 3)):
-        ar = arenas(0, 0)
+        ar = pool_arenas(PLAYOUT_OUT_SPECS, n, vec.device)
         ptrs = {k: a.t.data_ptr() for k, a in ar.items()}
         ptrs[bad] += phase
         assert call(ptrs) == SGX_EINVAL
@@ -233,9 +175,7 @@ def test_refusals_are_host_side():
     L = a._vec._L
     stream = a._vec._stream()
     idx = torch.zeros(n + 1, dtype=torch.int32, device='cuda')
-    outs = {'reward': torch.full((n, 2), 77.0, device='cuda'), 'done': torch.full((n,), 77, dtype=torch.uint8, device='cuda'),
-            'ending_invalid': torch.full((n,), 77, dtype=torch.uint8, device='cuda'), 'player': torch.full((n,), 77, dtype=torch.int8, device='cuda'),
-            'length': torch.full((n,), 77, dtype=torch.int32, device='cuda')}
+    outs = {k: torch.full((n, w) if w > 1 else (n,), 77, dtype=getattr(torch, t), device='cuda') for k, w, t in PLAYOUT_OUT_SPECS}
 
     def io(max_steps=0, flags=0, reward_off=0, length_off=0):
         return _lib.SgxPlayoutIO(outs['reward'].data_ptr() + reward_off, outs['done'].data_ptr(), outs['ending_invalid'].data_ptr(),
@@ -283,29 +223,12 @@ def test_refusals_are_host_side():
         x.close()
 
 
-def _pool_from(env, name, n):
-    """a pool holding the records of `env` (None: of a fresh env after reset())"""
-    from stratego_env_amd.procedural_env import PackedStates
-    from stratego_env_amd.vec_env import VecStrategoEnv
-    own = env is None
-    if own:
-        env = VecStrategoEnv(name, n, seed=1, auto_reset=False, human_inits=False, placement='plain')
-        env.reset()
-    pool = PackedStates(name, n)
-    st, pl = env.export_state()
-    pool._vec.import_state(st, pl)
-    if own:
-        env.close()
-    return pool
-
-
 @pytest.mark.parametrize('name', ['c7x7', 'c12x12'])
 def test_generic_geometries(name):
     """boards outside the reference's variants run the same kernel from their own library: 7x7 (two games per wave), 12x12 (one)"""
     import torch
     from stratego_env_amd.procedural_env import PackedStates
     from stratego_env_amd.vec_env import VecStrategoEnv
-    from tests.test_gpu_generic_geometry import CUSTOM
     v = CUSTOM[name]
     n = 16
     env = VecStrategoEnv(v, n, seed=23, auto_reset=False, human_inits=False, placement='plain')

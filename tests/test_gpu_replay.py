@@ -9,46 +9,14 @@ import numpy as np
 import pytest
 
 from tests import replay_rule as rr
-from tests.helpers import load_games
-from tests.test_gpu_playout import CASES, GAMES_PER_WORKGROUP, N_SRC, _np, _roots
+from tests.guard_bands import Arena, pool_arenas, pool_output_sweep
+from tests.pool_roots import (CASES, GAMES_PER_WORKGROUP, GOLDEN, N_SRC, _golden, _golden_roots, _layouts, _np, _pool_from, _ragged_lists, _replay_results,
+                              _roots)
 
 pytestmark = pytest.mark.gpu
 
 SGX_EINVAL = -1
-MASK = 'valid_actions_mask'
-GOLDEN = ['barrage', 'standard', 'micro', 'tiny', 'fives', 'medium', 'octa_barrage', 'short_barrage', 'short_standard', 'standard2']
 GOLDEN_WITH_INVALID = GOLDEN[2:]
-# lanes per game of the logic-only launches (Geo::LPG: 16 on boards of up to 16 cells, 32 up to 32 cells and on the two-games-per-wave
-# variant of the boards up to 128 cells, else 64): the size of the kernel's prefetch chunk
-LPG = {'micro': 16, 'tiny': 16, 'fives': 32, 'medium': 32, 'octa_barrage': 32, 'short_barrage': 32, 'barrage': 32, 'standard2': 64}
-
-
-def _results(res):
-    return {'applied': _np(res.applied), 'consumed': _np(res.consumed), 'stop': _np(res.stop), 'reward': _np(res.reward),
-            'done': _np(res.done), 'ending_invalid': _np(res.ending_invalid), 'player': _np(res.player)}
-
-
-def _golden(name):
-    """-> (g, actions int32 [n, longest] padded with -1, lengths int32 [n], errors per game)"""
-    g = load_games(name)
-    off = g['offsets']
-    n = len(off) - 1
-    lengths = (off[1:] - off[:-1]).astype(np.int32)
-    acts = np.full((n, int(lengths.max())), -1, dtype=np.int32)
-    errs = []
-    for gi in range(n):
-        acts[gi, :lengths[gi]] = g['actions'][off[gi]:off[gi + 1]]
-        errs.append(g['errors'][off[gi]:off[gi + 1]].astype(bool))
-    return g, acts, lengths, errs
-
-
-def _golden_roots(name, g):
-    import torch
-    from stratego_env_amd.vec_env import VecStrategoEnv
-    n = len(g['offsets']) - 1
-    env = VecStrategoEnv(name, n, seed=1, auto_reset=False, human_inits=False, placement='plain')
-    env.reset(torch.from_numpy(g['p1_maps'][:n]), torch.from_numpy(g['p2_maps'][:n]))
-    return env
 
 
 # ---- A: the golden games, one launch per variant, skip mode ---------------------------------------------------------------------------------
@@ -63,7 +31,7 @@ def test_golden_games_in_one_launch(name):
     pool = PackedStates(name, n)
     res = pool.replay(env, torch.from_numpy(acts).cuda(), lengths=torch.from_numpy(lengths).cuda(), skip_invalid=True)
     assert pool.last_launch_kind == _lib.LAUNCH_REPLAY
-    got = _results(res)
+    got = _replay_results(res)
     n_err = np.asarray([int(e.sum()) for e in errs], dtype=np.int32)
     print(name, 'games', n, 'moves', int(lengths.sum()), 'invalid', int(n_err.sum()))
     assert np.array_equal(got['consumed'], lengths), "consumed == len exactly (more: a read past a list)"
@@ -98,7 +66,7 @@ def test_golden_games_stop_at_their_first_invalid_entry(name):
     states, players = (_np(t) for t in env.export_state())
     pool = PackedStates(name, n)
     res = pool.replay(env, torch.from_numpy(acts).cuda(), lengths=torch.from_numpy(lengths).cuda())
-    got = _results(res)
+    got = _replay_results(res)
     first = np.asarray([int(np.flatnonzero(e)[0]) if e.any() else len(e) for e in errs], dtype=np.int32)
     assert np.array_equal(got['consumed'], first) and np.array_equal(got['applied'], first)
     assert np.array_equal(got['stop'], np.asarray([2 if e.any() else 0 for e in errs], dtype=np.uint8))
@@ -112,7 +80,7 @@ def _compare(variant, pool, res, states, players, acts, lengths, index, flags, w
     if want is None:
         want = rr.replay_batch(variant, states, players, acts, lengths, index, **flags)
     want_s, want_p, want_r, want_d, want_e, want_m, want_c, want_stop = want
-    got = _results(res)
+    got = _replay_results(res)
     assert np.array_equal(got['consumed'], want_c), (where, got['consumed'].tolist(), want_c.tolist())
     assert np.array_equal(got['applied'], want_m), where
     assert np.array_equal(got['stop'], want_stop), where
@@ -126,70 +94,6 @@ def _compare(variant, pool, res, states, players, acts, lengths, index, flags, w
 
 
 # ---- C: ragged inputs against the rule ---------------------------------------------------------------------------------------------------------
-def _make_list(name, state, player, length, rs, inject):
-    """A list of `length` entries from a position: random valid moves played forward by the oracle; `inject`: one entry is invalid instead
-    (-1, the number of spatial actions, or an in-range move the mask refuses) and the position stays; after the end of the game the list
-    goes on with arbitrary in-range entries.  -> (flat spatial entries in the mover's perspective, the same list as absolute 1-D indices)"""
-    env = rr._env(name)
-    ru = env.rules
-    NA, AS = env.rows * env.columns * env.K, ru.action_size
-    obs = env.reset(initial_state_override=np.asarray(state, dtype=np.int64), first_player_override=int(player))
-    sp, d1 = [], []
-    inj_at = int(rs.randint(length)) if (inject and length > 0) else -1
-    for t in range(length):
-        if ru.get_game_ended(env.state, 1) != 0:
-            sp.append(int(rs.randint(NA))); d1.append(int(rs.randint(AS)))
-            continue
-        mask = np.asarray(obs[env.player][MASK]).reshape(-1)
-        if t == inj_at:
-            kind = int(rs.randint(3))
-            if kind == 0:
-                sp.append(-1); d1.append(-1)
-            elif kind == 1:
-                sp.append(NA); d1.append(AS)
-            else:
-                zeros = np.flatnonzero(mask == 0)
-                sp.append(int(zeros[rs.randint(len(zeros))]))
-                zeros1 = np.flatnonzero(ru.get_valid_moves_as_1d_mask(env.state, env.player) == 0)
-                d1.append(int(zeros1[rs.randint(len(zeros1))]))
-            continue
-        valid = np.flatnonzero(mask)
-        a = int(valid[rs.randint(len(valid))])
-        spatial = tuple(int(x) for x in np.unravel_index(a, (env.rows, env.columns, env.K)))
-        sp.append(a)
-        d1.append(ru.get_action_1d_index_from_player_perspective(ru.get_action_1d_index_from_spatial_index(spatial), env.player))
-        obs, _, _, _ = env.step({env.player: a})
-    return sp, d1
-
-
-def _ragged_lists(name, states, players, idx, rs):
-    """-> (spatial int32 [n, L], 1-D int32 [n, L], lengths int32 [n]); the padding holds a valid-looking 0"""
-    lpg = LPG[name]
-    choices = (0, 1, lpg - 1, lpg, lpg + 1, 2 * lpg + 3)
-    n = len(idx)
-    lengths = np.asarray([choices[(i + int(rs.randint(2))) % 6] for i in range(n)], dtype=np.int32)
-    L = 2 * lpg + 3
-    sp = np.zeros((n, L), dtype=np.int32)
-    d1 = np.zeros((n, L), dtype=np.int32)
-    for i, s in enumerate(idx):
-        a, b = _make_list(name, states[s], players[s], int(lengths[i]), rs, inject=(i % 3 == 1))
-        sp[i, :lengths[i]], d1[i, :lengths[i]] = a, b
-    return sp, d1, lengths
-
-
-def _layouts(acts, torch):
-    """the list tensor in two layouts: dense game-major with a game stride beyond the longest list, and the transposed view of [L, n]"""
-    n, L = acts.shape
-    wide = torch.full((n, L + 5), -7, dtype=torch.int32, device='cuda')
-    wide[:, :L] = torch.from_numpy(acts).cuda()
-    dense = wide[:, :L]
-    assert dense.stride() == (L + 5, 1)
-    tn = torch.from_numpy(np.ascontiguousarray(acts.T)).cuda()
-    transposed = tn.T
-    assert transposed.stride() == (1, n) and tuple(transposed.shape) == (n, L)
-    return (('dense', dense, wide), ('transposed', transposed, tn))
-
-
 @pytest.mark.parametrize('name', list(CASES))
 def test_bit_exact_against_the_rule_on_ragged_lists(name):
     import torch
@@ -254,11 +158,11 @@ def test_the_in_place_call_equals_pool_to_pool():
         assert np.array_equal(_np(src.unpack()[0]), states)
         res = dst.replay(src, acts_t, lengths=lengths_t, skip_invalid=skip)
         want = _compare(name, dst, res, states, players, sp, lengths, None, dict(skip_invalid=skip), (name, 'pool to pool', skip))
-        pool_r = _results(res)
+        pool_r = _replay_results(res)
         assert np.array_equal(_np(src.unpack()[0]), states)              # src is only read
         res2 = src.replay(src, acts_t, lengths=lengths_t, skip_invalid=skip)
         _compare(name, src, res2, states, players, sp, lengths, None, dict(skip_invalid=skip), (name, 'in place', skip), want)
-        for k, v in _results(res2).items():
+        for k, v in _replay_results(res2).items():
             assert v.tobytes() == pool_r[k].tobytes(), k
     with pytest.raises(ValueError):
         src.replay(src, acts_t, src_index=torch.zeros(N_SRC, dtype=torch.int32, device='cuda'))
@@ -342,7 +246,6 @@ def test_null_outputs_and_guard_bands():
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena
     name, n = 'fives', 37
     env, states, players, finished = _roots(name, CASES[name][0], n=n)
     rs = np.random.RandomState(2)
@@ -353,52 +256,28 @@ def test_null_outputs_and_guard_bands():
     L = vec._L
     want = dict(zip(('state', 'player', 'reward', 'done', 'ending_invalid', 'applied', 'consumed', 'stop'),
                     rr.replay_batch(name, states, players, sp, lengths, None, skip_invalid=True)))
-    dtypes = {'float32': torch.float32, 'uint8': torch.uint8, 'int8': torch.int8, 'int32': torch.int32}
 
-    def arenas(byte_phase, word_phase):
-        ar = {k: Arena(k, (n, w) if w > 1 else (n,), dtypes[t], word_phase if t in ('float32', 'int32') else byte_phase, vec.device)
-              for k, w, t in OUT_SPECS}
+    def guarded_inputs(byte_phase, word_phase):
         ins = {'actions': Arena('actions', (n, Lmax), torch.int32, word_phase, vec.device), 'lengths': Arena('lengths', (n,), torch.int32, word_phase, vec.device)}
         ins['actions'].t.copy_(torch.from_numpy(sp))
         ins['lengths'].t.copy_(torch.from_numpy(lengths))
-        return ar, ins
+        return ins
 
     def call(ptrs, ins):
         io = _lib.SgxReplayIO(ins['actions'].t.data_ptr(), ins['lengths'].t.data_ptr(), ptrs['applied'], ptrs['consumed'], ptrs['stop'], ptrs['reward'],
                               ptrs['done'], ptrs['ending_invalid'], ptrs['player'], Lmax, 1, n * Lmax, Lmax, _lib.REPLAY_SKIP_INVALID)
         return L.sgx_replay(vec._h, env._h, None, io, vec._stream())
 
-    def check_inputs(ins):
+    def after_call(ins, skip):
         for a in ins.values():
             a.check_guards('sgx_replay')
         assert np.array_equal(ins['actions'].host(), sp) and np.array_equal(ins['lengths'].host(), lengths)
+        assert np.array_equal(_np(pool.unpack()[0]), want['state'])
 
-    # the tensors between guard bands, at every phase the contract allows
-    for byte_phase, word_phase in ((0, 0), (1, 4), (3, 12), (13, 0)):
-        ar, ins = arenas(byte_phase, word_phase)
-        assert call({k: a.t.data_ptr() for k, a in ar.items()}, ins) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        check_inputs(ins)
-        for k, a in ar.items():
-            a.check_guards('sgx_replay')
-            a.check_written('sgx_replay')
-            assert a.host().tobytes() == want[k].tobytes(), (k, byte_phase, word_phase)
-        assert np.array_equal(_np(pool.unpack()[0]), want['state'])
-    # each result pointer NULL in turn: the others are still right
-    for skip in [k for k, _, _ in OUT_SPECS]:
-        ar, ins = arenas(0, 0)
-        assert call({k: (None if k == skip else a.t.data_ptr()) for k, a in ar.items()}, ins) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        check_inputs(ins)
-        for k, a in ar.items():
-            a.check_guards('sgx_replay')
-            if k == skip:
-                a.check_untouched('sgx_replay')
-            else:
-                assert a.host().tobytes() == want[k].tobytes(), (k, 'without', skip)
-        assert np.array_equal(_np(pool.unpack()[0]), want['state'])
+    # the tensors between guard bands, at every phase the contract allows; then each result pointer NULL in turn: the others are still right
+    pool_output_sweep(OUT_SPECS, vec.device, guarded_inputs, call, want, 'sgx_replay', after_call)
     # lengths NULL: every list is max_len long
-    ar, ins = arenas(0, 0)
+    ar, ins = pool_arenas(OUT_SPECS, n, vec.device), guarded_inputs(0, 0)
     io = _lib.SgxReplayIO(ins['actions'].t.data_ptr(), None, ar['applied'].t.data_ptr(), ar['consumed'].t.data_ptr(), ar['stop'].t.data_ptr(), None, None, None, None,
                           Lmax, 1, n * Lmax, 5, _lib.REPLAY_SKIP_INVALID)
     assert L.sgx_replay(vec._h, env._h, None, io, vec._stream()) == 0, L.sgx_last_error()
@@ -415,7 +294,6 @@ def test_refusals_are_host_side():
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_playout import _pool_from
     name, n, Lmax = 'barrage', 16, 6
     env, states, players, _ = _roots(name, 30, n=n)
     a, b = _pool_from(env, name, n), _pool_from(env, name, n)

@@ -12,8 +12,8 @@ import pytest
 from oracle import oracle as orc
 from stratego_env_amd.config import VARIANTS
 from tests.helpers import GOLDEN, general_states
-from tests.test_gpu_trajectory import _host, _multi_kinds, _poison
-from tests.test_start_pool_cpu import CASES, G0, POOL_N, SEED, PoolFollower, make_pool
+from tests.step_checks import _host, _multi_kinds, _poison
+from tests.pool_roots import START_POOL_CASES as CASES, G0, POOL_N, SEED, PoolFollower, make_pool
 
 pytestmark = pytest.mark.gpu
 CHUNK = 64
@@ -218,7 +218,7 @@ def test_step_sync_with_four_envs():
 def test_a_board_of_more_than_256_cells():
     """17 x 16 = 272 cells (10-bit cell indices, records staged in a loop), 4 envs; the pool keeps its clock and sits a few moves before
     max_turns, so games end and restart all the time."""
-    from tests.test_gpu_generic_geometry import CUSTOM
+    from tests.boards import CUSTOM
     v = CUSTOM['c17x16']
     pool = make_pool(v, v.max_turns - 6, n=12)
     _rollout_against_follower('c17x16', 4, 96, None, False, 20, v=v, pool=pool)
@@ -385,7 +385,7 @@ def test_refusals():
 @pytest.mark.parametrize('name,n', [('barrage', 45), ('micro', 130), ('fives', 33)])
 def test_start_index_is_written_inside_its_extent_only(name, n):
     import torch
-    from tests.test_gpu_guard_bands import Arena
+    from tests.guard_bands import Arena
     from stratego_env_amd import _lib
     v = VARIANTS[name]
     states, players = make_pool(v, CASES[name][2])

@@ -3,31 +3,25 @@ numpy restatement of the rule on the oracle (tests/step_vs_rule.py, which tests/
 of four, two and one game per wave, a board with more channels than lanes and one with wide cells; a restatement-free check (T calls in
 place, then sgx_replay of the logged actions reproduces the records); NULL outputs, a ragged batch and guard bands, the in-place call
 against the two-handle call, the refusals (all host-side), a dst with a start pool, two tables on one stream; and the wrapper env.
-The stream contract of sgx_step_vs is held with tests/stream_gate.py by test_the_stream_contract below.  Its case is a row in the form of
-the table of tests/test_gpu_streams.py and is REGISTERED in that table when this module is imported (STREAM_CASE): tests/test_streams_cpu.py
-demands a row there for every prototype of the header that takes a stream, and this file is where the tests of sgx_step_vs live.  The
-registration happens at collection, so a run of tests/test_streams_cpu.py that collects neither this file nor tests/test_step_vs_cpu.py
-(which imports it) does not see the row.
+The stream contract of sgx_step_vs is the row `step-vs` of the one table of stream cases (tests/stream_cases.py, run by
+tests/test_gpu_streams.py).
 
-Roots, N_SRC, KEYS and DRAWS are taken as tests/test_gpu_weighted_playout.py takes them from tests/test_gpu_playout.py; a test restates at
-most two moves per slot."""
-import ctypes as C
+Roots, N_SRC, KEYS and DRAWS are the weighted playout tests' (tests/pool_roots.py); a test restates at most two moves per slot."""
 import itertools
 
 import numpy as np
 import pytest
 
 from stratego_env_amd import playout_policies as pol
-from tests import step_vs_rule as sv, test_gpu_playout as tp, test_gpu_streams as ts, test_gpu_weighted_playout as tw
-from tests.test_step_vs_cpu import agent_actions
+from tests import pool_roots as tp, step_vs_rule as sv, tables as tb
+from tests.guard_bands import Arena, pool_output_sweep
+from tests.pool_roots import STEP_VS_OUT_SPECS as OUT_SPECS, agent_actions
 
 pytestmark = pytest.mark.gpu
 
 SGX_EINVAL = -1
-N_SRC, KEYS, DRAWS, TABLES = tp.N_SRC, tp.KEYS, tp.DRAWS, tw.TABLES
+N_SRC, KEYS, DRAWS, TABLES = tp.N_SRC, tp.KEYS, tp.DRAWS, tb.TABLES
 OUTS = ('reward', 'done', 'ending_invalid', 'player', 'invalid_action', 'moved', 'reply_action')
-OUT_SPECS = (('reward', 2, 'float32'), ('done', 1, 'uint8'), ('ending_invalid', 1, 'uint8'), ('player', 1, 'int8'), ('invalid_action', 1, 'uint8'),
-             ('moved', 1, 'uint8'), ('reply_action', 1, 'int32'))
 # every value of every axis (table, view, agent) on each board; their whole cross product on the boards whose restatement is cheap
 SMALL = ('micro', 'fives', 'medium', 'octa_barrage', 'barrage')
 
@@ -56,12 +50,12 @@ def _compare(variant, pool, res, states, players, actions, sides, seed, offset, 
 
 
 def _roots_with_finished(name):
-    """tw._roots as a pool of N_SRC records; where the rollout left no finished game among them (the large boards), slots 0 .. 3 take the
+    """tp._board_roots as a pool of N_SRC records; where the rollout left no finished game among them (the large boards), slots 0 .. 3 take the
     ends of uniform playouts of their own games.  -> (pool, states, players, finished)"""
     import torch
     from stratego_env_amd.procedural_env import PackedStates
-    v = tw._variant(name)
-    env, states, players, finished = tw._roots(name, tw.CASES[name][0])
+    v = tp._board(name)
+    env, states, players, finished = tp._board_roots(name, tp.WEIGHTED_CASES[name][0])
     pool = PackedStates(v, N_SRC)
     pool.copy_from(env)
     if not finished.any():
@@ -83,7 +77,7 @@ def test_bit_exact_against_the_restatement(name):
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    v = tw._variant(name)
+    v = tp._board(name)
     env, states, players, finished = _roots_with_finished(name)
     assert finished.any() and not finished.all(), "both finished and unfinished roots"
     before_t = env.unpack()
@@ -187,9 +181,8 @@ def test_null_outputs_a_ragged_batch_and_guard_bands():
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena
     name, n = 'fives', 37
-    env, states, players, finished = tw._roots(name, tw.CASES[name][0], n=n)
+    env, states, players, finished = tp._board_roots(name, tp.WEIGHTED_CASES[name][0], n=n)
     pool = PackedStates(name, n, seed=2, env_id_offset=7)
     vec = pool._vec
     L = vec._L
@@ -197,50 +190,32 @@ def test_null_outputs_a_ragged_batch_and_guard_bands():
     actions = agent_actions(name, states, players, None, seed=3)[0]
     sides = _sides('mixed', n)
     want = dict(zip(('state', 'player') + OUTS[:3] + OUTS[4:], sv.step_vs_batch(name, states, players, actions, sides, 2, 7, 5, table, True)))
-    dtypes = {'float32': torch.float32, 'uint8': torch.uint8, 'int8': torch.int8, 'int32': torch.int32}
 
-    def arenas(byte_phase, word_phase):
-        ar = {k: Arena(k, (n, w) if w > 1 else (n,), dtypes[t], word_phase if t in ('float32', 'int32') else byte_phase, vec.device)
-              for k, w, t in OUT_SPECS}
+    def guarded_inputs(byte_phase, word_phase):
         ins = {'actions': Arena('actions', (n,), torch.int32, word_phase, vec.device), 'agent': Arena('agent', (n,), torch.int8, byte_phase, vec.device)}
         ins['actions'].t.copy_(torch.from_numpy(actions))
         ins['agent'].t.copy_(torch.from_numpy(sides))
-        return ar, ins
+        return ins
 
     def call(ptrs, ins):
         io = _vs_io(_lib, ptrs, ins['actions'].t.data_ptr(), ins['agent'].t.data_ptr(), 0, _lib.VS_SEE_ALL)
-        return L.sgx_step_vs(vec._h, env._h, None, io, tw._p16(table), 5, vec._stream())
+        return L.sgx_step_vs(vec._h, env._h, None, io, tb._p16(table), 5, vec._stream())
 
-    for byte_phase, word_phase in ((0, 0), (1, 4), (3, 12), (13, 0)):
-        ar, ins = arenas(byte_phase, word_phase)
-        assert call({k: a.t.data_ptr() for k, a in ar.items()}, ins) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        for k, a in ar.items():
-            a.check_guards('sgx_step_vs')
-            a.check_written('sgx_step_vs')
-            assert a.host().tobytes() == want[k].tobytes(), (k, byte_phase, word_phase)
-        for a in ins.values():
-            a.check_guards('sgx_step_vs')
-        assert np.array_equal(ins['actions'].host(), actions) and np.array_equal(ins['agent'].host(), sides)       # inputs only read
+    def after_call(ins, skip):
+        if skip is None:
+            for a in ins.values():
+                a.check_guards('sgx_step_vs')
+            assert np.array_equal(ins['actions'].host(), actions) and np.array_equal(ins['agent'].host(), sides)       # inputs only read
         assert np.array_equal(tp._np(pool.unpack()[0]), want['state'])
-    for skip in OUTS:
-        ar, ins = arenas(0, 0)
-        assert call({k: (None if k == skip else a.t.data_ptr()) for k, a in ar.items()}, ins) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        for k, a in ar.items():
-            a.check_guards('sgx_step_vs')
-            if k == skip:
-                a.check_untouched('sgx_step_vs')
-            else:
-                assert a.host().tobytes() == want[k].tobytes(), (k, 'without', skip)
-        assert np.array_equal(tp._np(pool.unpack()[0]), want['state'])
+
+    pool_output_sweep(OUT_SPECS, vec.device, guarded_inputs, call, want, 'sgx_step_vs', after_call)
     pool.close(); env.close()
 
 
 def test_in_place_equals_the_two_handle_call_and_null_actions():
     import torch
     name, n = 'barrage', 40
-    env, states, players, finished = tw._roots(name, 200, n=n)
+    env, states, players, finished = tp._board_roots(name, 200, n=n)
     twin = tp._pool_from(env, name, n)
     dst = tp._pool_from(None, name, n)
     actions = torch.from_numpy(agent_actions(name, states, players, None, seed=6)[0]).cuda()
@@ -269,7 +244,7 @@ def test_refusals_are_host_side_and_a_start_pool_is_accepted():
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
     name, n = 'barrage', 16
-    env, states, players, _ = tw._roots(name, 30, n=n)
+    env, states, players, _ = tp._board_roots(name, 30, n=n)
     a, b = tp._pool_from(env, name, n), tp._pool_from(env, name, n)
     foreign, small = PackedStates('standard', n), PackedStates(name, n // 2)
     L = a._vec._L
@@ -290,7 +265,7 @@ def test_refusals_are_host_side_and_a_start_pool_is_accepted():
         assert all(w in msg for w in ('sgx_step_vs',) + words), msg
 
     def call(dst, src, index, io_, table=good):
-        return L.sgx_step_vs(dst, src, index, io_, None if table is None else tw._p16(table), 0, stream)
+        return L.sgx_step_vs(dst, src, index, io_, None if table is None else tb._p16(table), 0, stream)
 
     ah, bh = a._vec._h, b._vec._h
     refused(call(ah, foreign._vec._h, None, io()), 'different variants')
@@ -347,7 +322,7 @@ def test_two_tables_on_one_stream():
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates, StepVsResult
     name, n = 'fives', N_SRC
-    env, states, players, finished = tw._roots(name, tw.CASES[name][0])
+    env, states, players, finished = tp._board_roots(name, tp.WEIGHTED_CASES[name][0])
     first, second = PackedStates(name, n, seed=4, env_id_offset=9), PackedStates(name, n, seed=4, env_id_offset=9)
     L = first._vec._L
     res = [StepVsResult.empty(n, 'cuda') for _ in range(2)]
@@ -356,9 +331,9 @@ def test_two_tables_on_one_stream():
     buf = TABLES['attacks'].copy()
     stream = first._vec._stream()
     assert second._vec._stream().value == stream.value                     # one stream for both calls
-    assert L.sgx_step_vs(first._vec._h, env._h, None, ios[0], tw._p16(buf), 6, stream) == 0, L.sgx_last_error()
+    assert L.sgx_step_vs(first._vec._h, env._h, None, ios[0], tb._p16(buf), 6, stream) == 0, L.sgx_last_error()
     buf[:] = TABLES['forward']                                             # the first call's table is gone
-    assert L.sgx_step_vs(second._vec._h, env._h, None, ios[1], tw._p16(buf), 6, stream) == 0, L.sgx_last_error()
+    assert L.sgx_step_vs(second._vec._h, env._h, None, ios[1], tb._p16(buf), 6, stream) == 0, L.sgx_last_error()
     buf[:] = 0
     torch.cuda.synchronize()
     acts = tp._np(actions)
@@ -366,38 +341,6 @@ def test_two_tables_on_one_stream():
     _compare(name, second, res[1], states, players, acts, -1, 4, 9, 6, TABLES['forward'], False, None, 'second')
     assert not torch.equal(res[0].reply_action, res[1].reply_action), "the two tables reply differently"
     first.close(); second.close(); env.close()
-
-
-def _stream_case(c):
-    """dst holds A until the call writes it; src, the index list, the agent's actions and sides go from A to B behind the gate (in A the
-    agent is each root's mover: its move, then the reply; in B it is the other side: the bot alone)"""
-    import torch
-    from stratego_env_amd import _lib
-    M, L, n = c.M, c.M.L, c.M.n
-    dst, src, si, idx = ts._pools(c)
-    actions = c.inp(*(M.act[X][idx[X].long()] for X in 'AB'))            # each root's own valid action (written on S)
-    agent = c.inp(*(torch.where(M.player[X][idx[X].long()] * s > 0, 1, -1).to(torch.int8) for X, s in (('A', 1), ('B', -1))))
-    outs = [c.new((n, w) if w > 1 else (n,), getattr(torch, t)) for _, w, t in OUT_SPECS]
-    io = _lib.SgxVsIO(actions.data_ptr(), agent.data_ptr(), *[t.data_ptr() for t in outs], 0, 0)
-    w = np.ascontiguousarray(np.random.RandomState(3).randint(1, 4096, size=_lib.PLAYOUT_WEIGHTS_SHAPE), dtype=np.uint16)   # (host memory)
-    c.keep.append(w)
-    c.call = lambda sp, s: ts._chk(c, L.sgx_step_vs(dst._h, src._h, ts._p(si), C.byref(io), w.ctypes.data_as(C.POINTER(C.c_uint16)), 9, sp))
-
-
-STREAM_CASE = ts._case('step-vs', 'sgx_step_vs', 'barrage', ts.N_BARRAGE, _stream_case)
-if all(c.id != STREAM_CASE.id for c in ts.CASES):
-    ts.CASES.append(STREAM_CASE)                   # the one table of stream cases (tests/test_streams_cpu.py reads it)
-
-
-def test_the_stream_contract():
-    """Twin, gated run and NULL-stream control (tests/stream_gate.py: run_case): all work of the call lands on the given stream, and the
-    call -- the gated run is the second one with these shapes -- returns while the gate still holds the stream."""
-    import torch
-    from tests import stream_gate as sg
-    torch.cuda.set_device(0)
-    case = sg.Case(sg.material(STREAM_CASE.variant, STREAM_CASE.n))
-    STREAM_CASE.build(case)
-    sg.run_case(case, may_wait=STREAM_CASE.may_wait, label=STREAM_CASE.id)
 
 
 def _follow(vs, variant, g, seed, steps_log):

@@ -20,8 +20,9 @@ import pytest
 from oracle import oracle as orc
 from stratego_env_amd.config import VARIANTS
 from tests.helpers import oracle_cvariant
-from tests.test_gpu_guard_bands import (Arena, _compare, _guards, _make, _phase_set, _play, _swap_outputs, _sync, _table, _written_after_step,
-                                        F32_QUAD_PHASES, I32_PHASES)
+from tests.boards import _table
+from tests.guard_bands import (Arena, F32_QUAD_PHASES, I32_PHASES, _compare, _guards, _make, _phase_set, _play, _swap_outputs, _sync,
+                               _written_after_step)
 
 pytestmark = pytest.mark.gpu
 

@@ -10,169 +10,24 @@ multi-step kernels do not cover (one launch per step behind the same entry point
 import numpy as np
 import pytest
 
-from oracle import oracle as orc
 from stratego_env_amd.config import VARIANTS
-from tests.helpers import oracle_cvariant
-from tests.test_gpu_parity import _table
+from tests.step_checks import Follower, _host, _multi_kinds, _poison, check_every_step_vs_oracle
 
 pytestmark = pytest.mark.gpu
-MASK, POBS, FOBS = 'valid_actions_mask', 'partial_observation', 'full_observation'
-
-
-def _oracles(name, seed, g0, n, both=False):
-    v = VARIANTS[name]
-    cv = oracle_cvariant(name, setups=_table(name))
-    envs = []
-    for e in range(n):
-        oe = orc.OracleEnv(v.rows, v.columns, v.max_turns, v.obstacle_locations, v.piece_counts,
-                           observation_mode='both_observations' if both else 'partially_observable')
-        oe.reset(initial_state_override=orc.reset_state(cv, seed, g0 + e, 0))
-        oe.game_no = 0
-        envs.append(oe)
-    return cv, envs
-
-
-def _poison(traj):
-    import torch
-    for k, t in traj.items():
-        if t.dtype == torch.float32:
-            t.fill_(float('nan'))
-        elif t.dtype == torch.int32:
-            t.fill_(-12345)
-        else:
-            t.fill_(0x5A)
-
-
-class Follower:
-    """The oracle stepped alongside a batch of GPU games: check_slot() plays ONE step of every game on the oracle and compares it with one
-    slot of a trajectory buffer (already on the host)."""
-
-    def __init__(self, name, seed, g0, n, auto_reset, both=False, with_obs=True):
-        self.name, self.seed, self.g0, self.n, self.auto_reset, self.both = name, seed, g0, n, auto_reset, both
-        self.with_obs = with_obs               # False: the rollout writes no observation (the no-observation kernel kind): masks, results and draws only
-        self.cv, self.oenvs = _oracles(name, seed, g0, n, both)
-        self.cur = [oe._obs(1) for oe in self.oenvs]
-        self.finished = [False] * n            # (without auto-reset: a finished game only takes invalid actions from then on)
-        self.games_done = 0
-        self.steps = 0
-
-    def drawn(self, e):
-        """the action the rollout plays next for game e: k-th valid of the current mask, k from the counter RNG (maenv:830-834 for a batch)"""
-        oe = self.oenvs[e]
-        return orc.sample_action(self.cur[e][MASK].astype(np.uint8), self.seed, self.g0 + e, oe.game_no, int(oe.state[5, 0, 0]))
-
-    def check_reset(self, obs_h, mask_h, fobs_h=None):
-        for e in range(self.n):
-            o = self.cur[e]
-            assert np.array_equal(o[MASK], mask_h[e]) and o[POBS].tobytes() == obs_h[e].tobytes(), (self.name, 'reset', e)
-            assert fobs_h is None or o[FOBS].tobytes() == fobs_h[e].tobytes()
-
-    def check_slot(self, acts, h, s, what):
-        """acts[e]: the action game e plays in this step; h: dict of host arrays with a leading slot axis; s: the slot this step wrote."""
-        tag = (self.name, what, 'step', self.steps, 'slot', s)
-        for e, oe in enumerate(self.oenvs):
-            a = int(acts[e])
-            try:
-                if self.finished[e]:
-                    raise ValueError
-                o, rew, done, info = oe.step({oe.player: a})
-            except ValueError:
-                assert h['invalid_action'][s, e] == 1, tag + (e, a, 'the oracle raises, the GPU accepted')
-                assert h['done'][s, e] == (1 if self.finished[e] else 0), tag + (e,)
-                assert np.array_equal(self.cur[e][MASK], h['mask'][s, e]), tag + (e, 'mask after an invalid action')
-                assert not self.with_obs or self.cur[e][POBS].tobytes() == h['obs'][s, e].tobytes(), tag + (e, 'observation after an invalid action')
-                assert h['player'][s, e] == oe.player
-                assert h['actions'][s, e] == self.drawn(e), tag + (e, 'draw after an invalid action')
-                continue
-            assert h['invalid_action'][s, e] == 0, tag + (e, a, 'the GPU flags a move the oracle accepts')
-            assert bool(h['done'][s, e]) == done['__all__'], tag + (e, 'done')
-            if done['__all__']:
-                self.games_done += 1
-                assert (h['reward'][s, e, 0], h['reward'][s, e, 1]) == (rew[1], rew[-1]), tag + (e, 'reward')
-                assert bool(h['ending_invalid'][s, e]) == info[1]['game_result_was_invalid'], tag + (e, 'ending_invalid')
-                if self.auto_reset:
-                    oe.game_no += 1
-                    o = oe.reset(initial_state_override=orc.reset_state(self.cv, self.seed, self.g0 + e, oe.game_no))
-                else:
-                    self.finished[e] = True
-                    o = {oe.player: o[oe.player]}                     # both terminal observations: the mover's is what the slot holds
-            else:
-                assert h['reward'][s, e, 0] == 0 and h['reward'][s, e, 1] == 0 and h['ending_invalid'][s, e] == 0, tag + (e,)
-            p = oe.player
-            assert h['player'][s, e] == p, tag + (e, 'player')
-            assert np.array_equal(o[p][MASK], h['mask'][s, e]), tag + (e, 'mask')
-            assert not self.with_obs or o[p][POBS].tobytes() == h['obs'][s, e].tobytes(), tag + (e, 'observation')
-            if self.both:
-                assert o[p][FOBS].tobytes() == h['fobs'][s, e].tobytes(), tag + (e, 'full observation')
-            self.cur[e] = o[p]
-            assert h['actions'][s, e] == self.drawn(e), tag + (e, 'drawn action')
-        self.steps += 1
-
-
-def _host(traj):
-    return {k: t.cpu().numpy() for k, t in traj.items()}
-
-
-MULTI = None
-
-
-def _multi_kinds():
-    from stratego_env_amd import _lib
-    return (_lib.LAUNCH_MULTI_STEP_WAVE, _lib.LAUNCH_MULTI_STEP)
 
 
 @pytest.mark.parametrize('name,n_envs,chunk,n_calls,garbage', [
     ('barrage', 48, 64, 10, 0.2), ('standard', 16, 48, 8, 0.1), ('short_barrage', 64, 40, 8, 0.2), ('octa_barrage', 32, 64, 5, 0.2),
     ('medium', 40, 50, 6, 0.2), ('fives', 33, 30, 6, 0.2), ('standard2', 5, 24, 4, 0.1), ('tiny', 100, 64, 4, 0.2), ('micro', 130, 20, 8, 0.2),
 ])
-def test_every_step_of_a_multi_step_launch_equals_the_oracle(name, n_envs, chunk, n_calls, garbage, both=False, auto_reset=True, kw=None, emit_obs=True,
-                                                             seed_salt=0):
-    """Calls of `chunk` steps into a trajectory buffer of `chunk` slots: every slot of every call against the oracle.  Some games start
-    every call from a garbage action (flagged, state unchanged, the same draw again); games end and restart inside the launches and across
-    their boundaries."""
-    import torch
-    from stratego_env_amd.vec_env import VecStrategoEnv
-    v = VARIANTS[name]
-    seed, g0 = 0x7A3B00 + 97 * len(name) + n_envs + 104729 * seed_salt, 7000 + 13 * seed_salt       # (tools/soak_trajectory.py varies the salt)
-    env = VecStrategoEnv(name, n_envs, seed=seed, env_id_offset=g0, auto_reset=auto_reset, full_obs=both, **(kw or {}))
-    fo = Follower(name, seed, g0, n_envs, auto_reset, both, with_obs=emit_obs)
-    env.reset()
-    fo.check_reset(env.obs.cpu().numpy(), env.mask.cpu().numpy(), env.fobs.cpu().numpy() if both else None)
-    env.sample_valid_actions()
-    traj = env.alloc_trajectory(chunk)
-    rs = np.random.RandomState(11 + seed_salt)
-    NA = v.num_spatial_actions
-    for call in range(n_calls):
-        nxt = env.next_actions.cpu().numpy().copy()
-        for e in range(n_envs):
-            assert nxt[e] == fo.drawn(e), (name, call, e, 'the draw a call starts from')
-            if rs.rand() < garbage:
-                nxt[e] = int(rs.choice([rs.randint(NA), -1, NA + 5, rs.randint(v.cells) * v.spatial_channels + v.spatial_channels - 1]))
-        env.next_actions.copy_(torch.from_numpy(nxt))
-        _poison(traj)
-        env.rollout_trajectory(chunk, traj, emit_obs=emit_obs)
-        assert env.last_launch_kind in _multi_kinds(), (name, 'the test must not pass on the per-step kernel')
-        if not emit_obs:
-            assert bool(torch.isnan(traj['obs']).all()), 'a rollout without an observation pointer must not touch the observation slots'
-        h = _host(traj)
-        acts = nxt
-        for s in range(chunk):
-            fo.check_slot(acts, h, s, 'call %d' % call)
-            acts = h['actions'][s]
-        # the env's own views are the last slot
-        assert env.obs.data_ptr() == traj['obs'][chunk - 1].data_ptr() and torch.equal(env.next_actions, traj['actions'][chunk - 1])
-    st, pl = env.export_state()
-    assert np.array_equal(st.cpu().numpy(), np.stack([oe.state for oe in fo.oenvs])), (name, 'final states')
-    assert np.array_equal(pl.cpu().numpy(), np.asarray([oe.player for oe in fo.oenvs], dtype=np.int8))
-    if auto_reset:
-        assert fo.games_done > 0 or name in ('standard', 'standard2')
-    env.close()
+def test_every_step_of_a_multi_step_launch_equals_the_oracle(name, n_envs, chunk, n_calls, garbage):
+    check_every_step_vs_oracle(name, n_envs, chunk, n_calls, garbage)
 
 
 @pytest.mark.parametrize('name,n_envs,chunk,n_calls', [('barrage', 24, 48, 6), ('octa_barrage', 16, 40, 4), ('fives', 20, 30, 4)])
 def test_every_step_with_both_observations(name, n_envs, chunk, n_calls):
     """BOTH_OBSERVATIONS (the reference's default mode, maenv:53): steps_kernel<..., 1> writes the 79-channel observation as well."""
-    test_every_step_of_a_multi_step_launch_equals_the_oracle(name, n_envs, chunk, n_calls, 0.1, both=True)
+    check_every_step_vs_oracle(name, n_envs, chunk, n_calls, 0.1, both=True)
 
 
 @pytest.mark.parametrize('name,n_envs,chunk,n_calls', [('barrage', 45, 64, 8), ('standard', 19, 40, 6), ('octa_barrage', 33, 50, 4), ('medium', 47, 40, 5), ('tiny', 70, 30, 3)])
@@ -180,14 +35,14 @@ def test_every_step_of_a_rollout_without_observation(name, n_envs, chunk, n_call
     """Mask-only rollouts (no observation pointer): steps_kernel<..., 8> -- on boards of 33 .. 128 cells the TWO-games-per-wave layout
     (Geo<R, C, 2>), ragged batches so that a wave holds one game -- every step's mask, rewards, flags, player and drawn action against the
     oracle; the observation slots stay untouched."""
-    test_every_step_of_a_multi_step_launch_equals_the_oracle(name, n_envs, chunk, n_calls, 0.2, emit_obs=False)
+    check_every_step_vs_oracle(name, n_envs, chunk, n_calls, 0.2, emit_obs=False)
 
 
 @pytest.mark.parametrize('name,n_envs,chunk,n_calls', [('short_barrage', 48, 64, 4), ('micro', 96, 25, 3)])
 def test_every_step_without_auto_reset(name, n_envs, chunk, n_calls):
     """Without auto-reset a finished game stays finished: every later step of the launch draws the no-op of its one-entry mask, which is
     not playable -- flagged invalid, nothing changes."""
-    test_every_step_of_a_multi_step_launch_equals_the_oracle(name, n_envs, chunk, n_calls, 0.0, auto_reset=False)
+    check_every_step_vs_oracle(name, n_envs, chunk, n_calls, 0.0, auto_reset=False)
 
 
 @pytest.mark.parametrize('name,n_envs,n_steps', [('barrage', 12, 300), ('micro', 70, 530)])

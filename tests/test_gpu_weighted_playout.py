@@ -4,50 +4,28 @@ tests/test_weighted_playout_cpu.py holds to the rule's promises) bit for bit in 
 board with more channels than lanes and one with wide cells; ragged batches, the in-place call and the int64 API, NULL outputs and guard
 bands, the refusals (all host-side, before any launch), two tables on one stream, and the PIMC example with a biased policy.
 
-Roots are taken as tests/test_gpu_playout.py takes them (rollouts without auto-reset, its rollout lengths); the caps keep the restated moves
-of a test under about 60,000."""
-import ctypes as C
-
+Roots are taken as tests/test_gpu_playout.py takes them (tests/pool_roots.py: rollouts without auto-reset, its rollout lengths); the caps
+keep the restated moves of a test under about 60,000."""
 import numpy as np
 import pytest
 
 from stratego_env_amd import playout_policies as pol
-from tests import test_gpu_playout as tp, weighted_playout_rule as wr
-from tests.test_weighted_playout_cpu import attacks_only_table, forward_only_table, third_zero_table
+from tests import pool_roots as tp, weighted_playout_rule as wr
+from tests.guard_bands import pool_output_sweep
+from tests.boards import _board
+from tests.pool_roots import N_SRC, WEIGHTED_CASES, _board_roots, _sample_states
+from tests.tables import TABLES, _p16
 
 pytestmark = pytest.mark.gpu
 
 SGX_EINVAL = -1
-N_SRC = tp.N_SRC
-TABLES = {'random': third_zero_table(0), 'attacks': attacks_only_table(), 'forward': forward_only_table()}
-# board -> (rollout steps before the roots are taken, the max_steps of draw 0 / 1 / 2): test_gpu_playout's, a cap of 20 where it plays to the end
-CASES = {name: (tp.CASES[name][0], tuple(c if c else 20 for c in tp.CASES[name][1]))
-         for name in ('micro', 'fives', 'medium', 'octa_barrage', 'barrage', 'standard2')}
-CASES['c3x40'] = (100, (1, 7, 30))                         # K = 83 channels, two games of 32 lanes per wave: the cell's channels in slices
-CASES['c32x32'] = (40, (1, 7, 20))                         # 10-bit cells, 16 cells per lane
-CASES['c20x20'] = (40, (1, 7, 20))                         # the workgroup's LDS with the weight sums passes 64 KB
-
-
-def _variant(name):
-    if name.startswith('c'):
-        from tests.test_gpu_generic_geometry import CUSTOM
-        return CUSTOM[name]
-    return name
-
-
-def _roots(name, steps, n=N_SRC, seed=17):
-    return tp._roots(_variant(name), steps, n=n, seed=seed)
-
-
-def _p16(w):
-    return w.ctypes.data_as(C.POINTER(C.c_uint16))
 
 
 def _compare(variant, pool, res, states, players, seed, offset, draw, table, see_all, index, max_steps, where):
     """the pool's final states and the five result tensors against the restatement; -> (lengths, W == 0 positions, W > 0 positions)"""
     want_s, want_p, want_r, want_d, want_e, want_l, n_zero, n_pos = wr.playout_batch(variant, states, players, seed, offset, draw, table, see_all,
                                                                                       index, max_steps)
-    got = tp._results(res)
+    got = tp._playout_results(res)
     print(where, 'lengths', want_l.tolist())
     assert np.array_equal(got['length'], want_l), where
     assert got['reward'].tobytes() == want_r.tobytes(), where
@@ -65,8 +43,8 @@ def test_a_constant_table_plays_the_games_of_sgx_playout(name):
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    v = _variant(name)
-    env, states, players, finished = _roots(name, CASES[name][0])
+    v = _board(name)
+    env, states, players, finished = _board_roots(name, WEIGHTED_CASES[name][0])
     assert not finished.all()
     n = 61
     idx_t = torch.from_numpy(np.random.RandomState(5).randint(0, N_SRC, size=n).astype(np.int32)).cuda()
@@ -81,8 +59,8 @@ def test_a_constant_table_plays_the_games_of_sgx_playout(name):
                 got = weighted.playout(env, src_index=index_t, max_steps=max_steps, draw=draw, weights=np.full(wr.SHAPE, c), see_all=see_all)
                 assert weighted.last_launch_kind == _lib.LAUNCH_PLAYOUT_WEIGHTED
                 where = (name, seed, draw, c, see_all, max_steps)
-                for k, t in tp._results(want).items():
-                    assert tp._results(got)[k].tobytes() == t.tobytes(), (where, k)
+                for k, t in tp._playout_results(want).items():
+                    assert tp._playout_results(got)[k].tobytes() == t.tobytes(), (where, k)
                 ws, wp = weighted.unpack()
                 ps, pp = plain.unpack()
                 assert torch.equal(ws, ps) and torch.equal(wp, pp), where
@@ -97,9 +75,9 @@ def test_bit_exact_against_the_restatement(name):
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    v = _variant(name)
-    steps, caps = CASES[name]
-    env, states, players, finished = _roots(name, steps)
+    v = _board(name)
+    steps, caps = WEIGHTED_CASES[name]
+    env, states, players, finished = _board_roots(name, steps)
     assert not finished.all()
     before_t = env.export_state()
     n = 61
@@ -136,7 +114,7 @@ def test_bit_exact_against_the_restatement(name):
 def test_ragged_batches(name):
     import torch
     from stratego_env_amd.procedural_env import PackedStates
-    env, states, players, finished = _roots(name, CASES[name][0])
+    env, states, players, finished = _board_roots(name, WEIGHTED_CASES[name][0])
     wg = tp.GAMES_PER_WORKGROUP[name]
     rs = np.random.RandomState(3)
     table = TABLES['random']
@@ -152,7 +130,6 @@ def test_ragged_batches(name):
 def test_in_place_and_the_int64_api():
     import torch
     from stratego_env_amd.procedural_env import BatchedStrategoProceduralEnv
-    from tests.test_gpu_procedural import _sample_states
     table = TABLES['forward']
     for name, max_steps, see_all in (('fives', 0, True), ('barrage', 9, False)):
         n = 40
@@ -164,10 +141,10 @@ def test_in_place_and_the_int64_api():
         res = dst.playout(src, max_steps=max_steps, draw=3, weights=table, see_all=see_all)                # pool to pool
         want_l, _, _ = _compare(name, dst, res, states, players, 0, 0, 3, table, see_all, None, max_steps, (name, 'pool to pool'))
         assert (want_l == 0).any() and (want_l > 0).any()
-        pool_s, pool_r = tp._np(dst.unpack()[0]), tp._results(res)
+        pool_s, pool_r = tp._np(dst.unpack()[0]), tp._playout_results(res)
         res2 = src.playout(src, max_steps=max_steps, draw=3, weights=table, see_all=see_all)               # in place
         assert np.array_equal(tp._np(src.unpack()[0]), pool_s)
-        for k, val in tp._results(res2).items():
+        for k, val in tp._playout_results(res2).items():
             assert val.tobytes() == pool_r[k].tobytes(), (name, k)
         with pytest.raises(ValueError):
             src.playout(src, src_index=torch.zeros(n, dtype=torch.int32, device='cuda'), weights=table)
@@ -176,7 +153,7 @@ def test_in_place_and_the_int64_api():
         # int64 in, int64 out; a CPU tensor as the table
         res3, final, final_players = pe.playout(states, players, max_steps=max_steps, draw=3, return_states=True,
                                                 weights=torch.from_numpy(table.astype(np.int32)), see_all=see_all)
-        for k, val in tp._results(res3).items():
+        for k, val in tp._playout_results(res3).items():
             assert val.tobytes() == pool_r[k].tobytes(), (name, k)
         assert final.dtype == torch.int64 and np.array_equal(tp._np(final), pool_s)
         assert np.array_equal(tp._np(final_players), pool_r['player'])
@@ -188,43 +165,23 @@ def test_null_outputs_and_guard_bands():
     import torch
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
-    from tests.test_gpu_guard_bands import Arena
     name, n = 'fives', 37
-    env, states, players, finished = _roots(name, CASES[name][0], n=n)
+    env, states, players, finished = _board_roots(name, WEIGHTED_CASES[name][0], n=n)
     pool = PackedStates(name, n, seed=2, env_id_offset=7)
     vec = pool._vec
     L = vec._L
     table = TABLES['random']
     want = dict(zip(('state', 'player', 'reward', 'done', 'ending_invalid', 'length'), wr.playout_batch(name, states, players, 2, 7, 5, table, True)))
-    dtypes = {'float32': torch.float32, 'uint8': torch.uint8, 'int8': torch.int8, 'int32': torch.int32}
 
-    def arenas(byte_phase, word_phase):
-        return {k: Arena(k, (n, w) if w > 1 else (n,), dtypes[t], word_phase if t in ('float32', 'int32') else byte_phase, vec.device)
-                for k, w, t in tp.OUT_SPECS}
-
-    def call(ptrs):
+    def call(ptrs, ins):
         io = _lib.SgxPlayoutIO(ptrs['reward'], ptrs['done'], ptrs['ending_invalid'], ptrs['player'], ptrs['length'], 0, 0)
         return L.sgx_playout_weighted(vec._h, env._h, None, io, _p16(table), _lib.PLAYOUT_SEE_ALL, 5, vec._stream())
 
-    for byte_phase, word_phase in ((0, 0), (1, 4), (3, 12), (13, 0)):
-        ar = arenas(byte_phase, word_phase)
-        assert call({k: a.t.data_ptr() for k, a in ar.items()}) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        for k, a in ar.items():
-            a.check_guards('sgx_playout_weighted')
-            a.check_written('sgx_playout_weighted')
-            assert a.host().tobytes() == want[k].tobytes(), (k, byte_phase, word_phase)
-        assert np.array_equal(tp._np(pool.unpack()[0]), want['state'])
-    for skip in [k for k, _, _ in tp.OUT_SPECS]:
-        ar = arenas(0, 0)
-        assert call({k: (None if k == skip else a.t.data_ptr()) for k, a in ar.items()}) == 0, L.sgx_last_error()
-        torch.cuda.synchronize()
-        for k, a in ar.items():
-            a.check_guards('sgx_playout_weighted')
-            if k == skip:
-                a.check_untouched('sgx_playout_weighted')
-            else:
-                assert a.host().tobytes() == want[k].tobytes(), (k, 'without', skip)
+    def after_call(ins, skip):
+        if skip is None:
+            assert np.array_equal(tp._np(pool.unpack()[0]), want['state'])
+
+    pool_output_sweep(tp.PLAYOUT_OUT_SPECS, vec.device, lambda byte_phase, word_phase: {}, call, want, 'sgx_playout_weighted', after_call)
     pool.close(); env.close()
 
 
@@ -234,16 +191,14 @@ def test_refusals_are_host_side():
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
     name, n = 'barrage', 16
-    env, states, players, _ = _roots(name, 30, n=n)
+    env, states, players, _ = _board_roots(name, 30, n=n)
     a, b = tp._pool_from(env, name, n), tp._pool_from(env, name, n)
     foreign = PackedStates('standard', n)
     small = PackedStates(name, n // 2)
     L = a._vec._L
     stream = a._vec._stream()
     idx = torch.zeros(n + 1, dtype=torch.int32, device='cuda')
-    outs = {'reward': torch.full((n, 2), 77.0, device='cuda'), 'done': torch.full((n,), 77, dtype=torch.uint8, device='cuda'),
-            'ending_invalid': torch.full((n,), 77, dtype=torch.uint8, device='cuda'), 'player': torch.full((n,), 77, dtype=torch.int8, device='cuda'),
-            'length': torch.full((n,), 77, dtype=torch.int32, device='cuda')}
+    outs = {k: torch.full((n, w) if w > 1 else (n,), 77, dtype=getattr(torch, t), device='cuda') for k, w, t in tp.PLAYOUT_OUT_SPECS}
     good = pol.capture_biased(name)
 
     def io(max_steps=0, flags=0, reward_off=0, length_off=0):
@@ -303,7 +258,7 @@ def test_two_tables_on_one_stream():
     from stratego_env_amd import _lib
     from stratego_env_amd.procedural_env import PackedStates
     name, n = 'fives', N_SRC
-    env, states, players, finished = _roots(name, CASES[name][0])
+    env, states, players, finished = _board_roots(name, WEIGHTED_CASES[name][0])
     first, second = PackedStates(name, n, seed=4, env_id_offset=9), PackedStates(name, n, seed=4, env_id_offset=9)
     L = first._vec._L
     res = [[torch.empty((n, 2), dtype=torch.float32, device='cuda'), torch.empty((n,), dtype=torch.uint8, device='cuda'),

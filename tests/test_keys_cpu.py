@@ -194,7 +194,7 @@ def test_the_library_exports_the_entry_point():
 
 def test_the_new_kernels_use_no_scratch_memory_and_no_lds(tmp_path):
     """keys_kernel on every board of the reference, both key widths: no scratch memory, no LDS (read from the shipped library)"""
-    from tests.test_cabi_cpu import _kernel_resources
+    from tests.step_checks import _kernel_resources
     res = _kernel_resources(tmp_path)
     seen = set()
     for name, r in res.items():

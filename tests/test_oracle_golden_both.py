@@ -1,22 +1,12 @@
 """Oracle in observation_mode=BOTH_OBSERVATIONS vs vectors recorded from the reference (tools/oracle/gen_golden_both.py)."""
-import hashlib
-
 import numpy as np
 import pytest
 
 from oracle import oracle as orc
 from stratego_env_amd.config import VARIANTS
 from tests.helpers import _load_npz, GOLDEN, load_variants_json
+from tests.step_checks import digest_both
 import os
-
-
-def digest_both(obs):
-    h = hashlib.sha256()
-    for p in sorted(obs.keys()):
-        h.update(np.ascontiguousarray(obs[p]['valid_actions_mask']).astype(np.uint8).tobytes())
-        h.update(np.ascontiguousarray(obs[p]['partial_observation'], dtype=np.float32).tobytes())
-        h.update(np.ascontiguousarray(obs[p]['full_observation'], dtype=np.float32).tobytes())
-    return int.from_bytes(h.digest()[:8], 'little')
 
 
 def test_full_obs_norm_constants_match_reference():

@@ -9,7 +9,7 @@ import pytest
 from oracle import oracle as orc
 from stratego_env_amd.config import VARIANTS
 from tests.helpers import _load_npz, GOLDEN
-from tests.test_oracle_golden_both import digest_both
+from tests.step_checks import digest_both
 
 ORIG_VARIANTS = ['barrage', 'standard', 'tiny', 'micro', 'fives', 'octa_barrage']
 

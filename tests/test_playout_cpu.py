@@ -9,7 +9,7 @@ from oracle import oracle as orc
 from stratego_env_amd import _lib
 from stratego_env_amd.config import VARIANTS
 from tests import playout_rule as pr
-from tests.test_determinize_cpu import sampled_states
+from tests.pool_roots import sampled_states
 
 GAME_SETS = ['micro', 'tiny', 'fives']
 

@@ -14,42 +14,11 @@ from oracle import oracle as orc
 from stratego_env_amd import _lib, playout_policies as pol
 from stratego_env_amd.config import VARIANTS
 from tests import replay_rule as rr, step_vs_rule as sv, weighted_playout_rule as wr
-from tests.test_determinize_cpu import sampled_states
-from tests.test_weighted_playout_cpu import third_zero_table
+from tests.pool_roots import VALID, agent_actions, sampled_states
+from tests.tables import third_zero_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAME_SETS = ['micro', 'tiny', 'fives']
-VALID, OUT_OF_RANGE, WRONG_PIECE, NOOP = 0, 1, 2, 3
-
-
-def _variant(variant):
-    return VARIANTS[variant] if isinstance(variant, str) else variant
-
-
-def agent_actions(variant, states, players, index=None, seed=0):
-    """One action per slot for the mover of states[index[i]], a seeded mix: mostly a sampled valid action; else a value out of range, a
-    valid-looking move of the wrong piece (a move of the OPPONENT's mask, which the mover cannot make) or the no-op while a move exists.
-    -> (actions int32 [n], kinds [n]); a kind that a position does not offer falls back to VALID.  (The GPU test uses the same.)"""
-    v = _variant(variant)
-    K = v.spatial_channels
-    NA = v.rows * v.columns * K
-    noop = K - 1
-    idx = np.arange(len(states)) if index is None else np.asarray(index)
-    rs = np.random.RandomState(seed)
-    actions, kinds = np.empty(len(idx), dtype=np.int32), np.empty(len(idx), dtype=np.int64)
-    for i, s in enumerate(idx):
-        valid = sv.valid_actions(v, states[s], int(players[s]))
-        kind = int(rs.choice([VALID] * 5 + [OUT_OF_RANGE, WRONG_PIECE, NOOP]))
-        a = int(valid[rs.randint(len(valid))])
-        if kind == OUT_OF_RANGE:
-            a = int(rs.choice([-1, NA, NA + 5, 2 ** 31 - 1, -2 ** 31]))
-        elif kind == WRONG_PIECE:
-            theirs = np.setdiff1d(sv.valid_actions(v, states[s], -int(players[s])), np.append(valid, noop))
-            kind, a = (WRONG_PIECE, int(theirs[rs.randint(len(theirs))])) if len(theirs) else (VALID, a)
-        elif kind == NOOP:
-            kind, a = (NOOP, noop) if valid[0] != noop else (VALID, a)
-        actions[i], kinds[i] = a, kind
-    return actions, kinds
 
 
 def _over(name, st):
@@ -212,11 +181,3 @@ def test_replaying_the_two_actions_gives_the_final_state(name, stepped):
     assert replayed > 0
 
 
-def test_the_stream_case_is_registered():
-    """sgx_step_vs takes a stream: its case of the stream contract stands in tests/test_gpu_step_vs.py and is a row of the one table"""
-    from tests import test_gpu_step_vs as g, test_gpu_streams as ts
-    assert g.STREAM_CASE in ts.CASES and g.STREAM_CASE.entries == ('sgx_step_vs',) and not g.STREAM_CASE.may_wait
-    assert len({c.id for c in ts.CASES}) == len(ts.CASES)
-
-
-from tests import test_gpu_step_vs  # noqa: E402,F401  (at the end: that module imports agent_actions from here; importing it registers the stream case)

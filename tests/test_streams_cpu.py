@@ -1,10 +1,10 @@
-"""Completeness of tests/test_gpu_streams.py against the header: every prototype of include/stratego_mi355x.h that takes a `void *stream`
-is a row of the case table or stands in the exclusion list below with its reason, and the header's list of entry points that wait for
+"""Completeness of the table of stream cases (tests/stream_cases.py, run by tests/test_gpu_streams.py) against the header: every prototype of
+include/stratego_mi355x.h that takes a `void *stream` is a row of the table or stands in the exclusion list below with its reason, and the header's list of entry points that wait for
 the device is what the table marks may_wait.  A new entry point cannot ship without a stream case."""
 import os
 import re
 
-from tests.test_gpu_streams import CASES
+from tests.stream_cases import CASES
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'include', 'stratego_mi355x.h')
 
@@ -59,7 +59,7 @@ def test_every_stream_taking_entry_point_has_a_case_or_an_exclusion():
     assert not set(EXCLUDED) - takers, "exclusions that are no stream-taking prototypes: %s" % sorted(set(EXCLUDED) - takers)
     assert not covered & set(EXCLUDED), "excluded AND covered: %s" % sorted(covered & set(EXCLUDED))
     missing = takers - covered - set(EXCLUDED)
-    assert not missing, ("entry points that take a stream but have neither a case in tests/test_gpu_streams.py nor an exclusion with a reason "
+    assert not missing, ("entry points that take a stream but have neither a case in tests/stream_cases.py nor an exclusion with a reason "
                          "here: %s" % sorted(missing))
     assert all(len(reason) > 20 for reason in EXCLUDED.values())
 
@@ -73,4 +73,3 @@ def test_the_headers_waiting_list_is_what_the_table_marks():
     assert not may_wait & always_async, "marked may_wait in one row and asynchronous in another: %s" % sorted(may_wait & always_async)
     # of the stream-taking entry points, the header's list is the excluded measurement tools plus the rows marked may_wait -- both ways
     assert waits & takers == may_wait | set(EXCLUDED), (sorted(waits & takers), sorted(may_wait | set(EXCLUDED)))
-    assert len({c.id for c in CASES}) == len(CASES)

@@ -2,7 +2,6 @@
 (tests/weighted_playout_rule.py, what the device kernel is held to bit for bit in tests/test_gpu_weighted_playout.py) against the two
 consequences the rule promises -- a constant table plays sgx_playout's games, a weight of 0 is never drawn next to a positive one --, the
 two views, the distribution of the first move, and the ready-made tables of stratego_env_amd.playout_policies."""
-import ctypes as C
 import os
 import re
 
@@ -13,36 +12,11 @@ from oracle import oracle as orc
 from stratego_env_amd import _lib, playout_policies as pol
 from stratego_env_amd.config import VARIANTS
 from tests import draw_stats as ds, playout_rule as pr, weighted_playout_rule as wr
-from tests.test_determinize_cpu import sampled_states
+from tests.pool_roots import sampled_states
+from tests.tables import _p16, attacks_only_table, third_zero_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GAME_SETS = ['micro', 'tiny', 'fives']
-
-
-def third_zero_table(seed=0):
-    """A seeded random table, values to 4095, about 30 % of the entries 0 (the GPU test uses the same)."""
-    rs = np.random.RandomState(seed)
-    w = rs.randint(1, 4096, size=wr.SHAPE)
-    w[rs.random_sample(wr.SHAPE) < 0.3] = 0
-    return w.astype(np.uint16)
-
-
-def attacks_only_table():
-    """Weight 5 for a move onto an occupied cell (a known type, or unknown), 0 for a move onto an empty one."""
-    w = np.zeros(wr.SHAPE, dtype=np.uint16)
-    w[:, :, 1:] = 5
-    return w
-
-
-def forward_only_table():
-    """[8, 1, 1, 1] by direction"""
-    w = np.ones(wr.SHAPE, dtype=np.uint16)
-    w[0] = 8
-    return w
-
-
-def _p16(w):
-    return w.ctypes.data_as(C.POINTER(C.c_uint16))
 
 
 def test_the_binding():

@@ -1,4 +1,4 @@
-"""Soak of the per-step oracle pinning of the MULTI-STEP kernels (tests/test_gpu_trajectory.py): rollouts into trajectory buffers over fresh
+"""Soak of the per-step oracle pinning of the MULTI-STEP kernels (tests/step_checks.py: check_every_step_vs_oracle, what tests/test_gpu_trajectory.py runs): rollouts into trajectory buffers over fresh
 seeds, ragged batch sizes, chunk lengths and garbage rates -- every slot (mask, observation(s), rewards, flags, player, drawn action) against
 the oracle stepped alongside -- for a wall-clock budget.      python tools/soak_trajectory.py [seconds=300]"""
 import os
@@ -6,7 +6,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tests import test_gpu_trajectory as T  # noqa: E402
+from tests import step_checks as T  # noqa: E402
 
 # (name, envs, chunk, calls, garbage, both, emit_obs)
 PLAN = [('barrage', 41, 64, 8, 0.15, False, True), ('micro', 150, 30, 6, 0.2, False, True), ('standard', 11, 56, 6, 0.05, False, True),
@@ -25,7 +25,7 @@ def main():
     while time.time() - t0 < budget:
         for name, n, chunk, calls, g, both, emit_obs in PLAN:
             n_envs = n if n % 16 == 0 else n + salt % 5
-            T.test_every_step_of_a_multi_step_launch_equals_the_oracle(name, n_envs, chunk + salt % 7, calls, g, both=both, emit_obs=emit_obs, seed_salt=salt)
+            T.check_every_step_vs_oracle(name, n_envs, chunk + salt % 7, calls, g, both=both, emit_obs=emit_obs, seed_salt=salt)
             runs += 1
             steps += n_envs * (chunk + salt % 7) * calls
             if time.time() - t0 > budget:
